@@ -1,6 +1,11 @@
 """FIA influence-query throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config ml1m-mf|yelp-ncf|20m-mf64|20m-mf256|20m-ncf256]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, spins up and warms up, times the K steps, writes the last step's outputs
+if `--dump-outputs DIR` is given (dump_outputs) and prints the result line.  `--full` adds the
+measurements with runs of their own: the CPU baseline and the instrumented per-phase steps.
 
 A step = one pass of the hot path over one batch: per-entity Hessian caches
 (fia_prepare / fia_prepare_for), related-set counts + offsets (fia_count_related),
@@ -35,14 +40,14 @@ runs the whole hot path over the whole batch; the timed region is still K steps 
 synchronisations.  `value` = queries answered by all ranks / the max-over-ranks
 time of the timed steps.
 
-Rank 0 prints one JSON line.  `roofline` prices the step's dominant phase (from a few
-instrumented steps): the scoring phase against HBM -- `achieved` = its kernel's HBM
+Rank 0 prints one JSON line.  `roofline` prices the scoring phase, or with `--full` the step's
+dominant phase (from a few instrumented steps): the scoring phase against HBM -- `achieved` = its kernel's HBM
 bytes per launch measured by rocprofv3 PMC (FETCH_SIZE x 2 + WRITE_SIZE,
 MI355X_MICROARCH.md's gfx950 correction; profiles/traffic.json, tools/traffic_json.py)
 over its HIP-event duration in this run, `frac` = achieved / 8 TB/s, with SURVEY 8d's
 algorithmic byte count beside it under `algorithmic` -- or a solve / prepare phase
 against the FP64 peak (algorithmic flops over its event time).
-`cpu_baseline` times the reference ALGORITHM (oracle/ncg_port.py) on a bounded
+`cpu_baseline` (`--full`) times the reference ALGORITHM (oracle/ncg_port.py) on a bounded
 sample on this host, with two more CPU figures under `variants`.
 """
 import argparse
@@ -116,8 +121,16 @@ def parse(argv=None):
                          "6 otherwise): a fresh MI355X runs the HBM-heavy scoring kernels ~15 %% slower for its "
                          "first ~30 s of load, and the sub-ms ml-1m-ex / yelp-ex steps ~4 %% slower over the "
                          "driver's 5 + 20 steps than after 1 s of load (same-box A/B, tools/evt_ab.sh)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baseline (before the GPU is "
+                         "touched) and the per-phase breakdown from instrumented steps, with the roofline of the "
+                         "step's dominant phase (`cpu_baseline`, `phases_ms_per_step`, `phases_ms_per_launch`, "
+                         "`roofline.isolated`)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                         "(float64; seeded samples of the large arrays, see dump_outputs)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--rank-set", type=int, default=0,
                     help="answer the query set weak-scaling rank R > 0 answers (check its cost on one GPU)")
     ap.add_argument("--cpu-procs", type=int, default=0,
@@ -129,7 +142,10 @@ def parse(argv=None):
                     help="RQ2 single-query latency instead of the throughput line: ml-1m-ex test_idx 59 and "
                          "yelp-ex test_idx 1, MF and NCF k=16 (reference src/scripts/RQ2.py:53,57), GPU through "
                          "the facade beside the reference algorithm's CPU time for the same query")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def _free_port():
@@ -429,6 +445,48 @@ def compulsory_bytes(cfg, qu, qi, deg_u, deg_i, bounds):
     return tot / max(len(bounds) - 1, 1)
 
 
+DUMP_MAX_ELEMS = 1 << 19     # per array: 4 MiB of float64; at most ten arrays, so < 64 MB in all
+
+
+def dump_outputs(path, lane, batch, Q, K, D):
+    """--dump-outputs: what the last timed step left in its lane's output buffers, i.e. what a
+    caller of the hot path receives, as float64 .npy files (integers are exact in float64):
+      offsets       related-set offsets of the step's last query batch (its queries + 1)
+      influence     influence of every related rating of that batch
+      rel_idx       their train rows
+      inverse_hvp   the batch's inverse HVPs (queries x D)
+      topk_pos / topk_idx / topk_val   the per-query top-K lists of the whole query set
+    (rel / influence / inverse-HVP buffers are reused batch to batch, so a multi-batch step leaves
+    its last batch there.)  An array of more than DUMP_MAX_ELEMS elements is written as a fixed
+    sample: the elements at the sorted positions drawn by default_rng(0), the positions
+    themselves beside it as <name>_pos.npy (influence and rel_idx share influence_pos)."""
+    import torch
+    b0, b1, _, _, off_b, tot_b = batch
+    os.makedirs(path, exist_ok=True)
+
+    def put(name, t, pos=None):
+        if pos is not None:
+            t = t[torch.from_numpy(pos).to(t.device)]
+        a = t.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, np.float64))
+
+    def positions(name, n):
+        if n <= DUMP_MAX_ELEMS:
+            return None
+        pos = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ELEMS, replace=False))
+        np.save(os.path.join(path, name + "_pos.npy"), pos.astype(np.float64))
+        return pos
+
+    put("offsets", off_b[:b1 - b0 + 1], positions("offsets", b1 - b0 + 1))
+    pos = positions("influence", int(tot_b))
+    put("influence", lane["infl"][:tot_b], pos)
+    put("rel_idx", lane["rel"][:tot_b], pos)
+    put("inverse_hvp", lane["xbuf"][:(b1 - b0) * D], positions("inverse_hvp", (b1 - b0) * D))
+    pos = positions("topk", Q * K)
+    for name, buf in (("topk_pos", "tp"), ("topk_idx", "tix"), ("topk_val", "tv")):
+        put(name, lane[buf][:Q * K], pos)
+
+
 def rq2_main(args):
     """RQ2 (reference src/scripts/RQ2.py, experiments.record_time_cost): the latency of ONE
     query -- ml-1m-ex test_idx 59, yelp-ex test_idx 1, MF and NCF k=16 -- as the reference times
@@ -498,7 +556,7 @@ def main():
 
     d, params = load_data(cfg)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # before anything touches the GPU: the baseline's workers are forked from this process
         cpu = cpu_baseline(cfg, d, params, args.cpu_baseline_seconds, args.cpu_procs or cpu_cores())
 
@@ -678,16 +736,18 @@ def main():
         return tot
 
     read_all()
-    for L in lanes:
-        L["ctx"].set_profiling(True)
-    # (instrumented steps one at a time: the per-phase breakdown of an un-overlapped step)
+    phases = {}
     n_instr = max(1, min(args.steps, 5))
-    for _ in range(n_instr):
-        compute()
-        torch.cuda.synchronize(dev)
-    for L in lanes:
-        L["ctx"].set_profiling(False)
-    phases = read_all()
+    if args.full:
+        for L in lanes:
+            L["ctx"].set_profiling(True)
+        # (instrumented steps one at a time: the per-phase breakdown of an un-overlapped step)
+        for _ in range(n_instr):
+            compute()
+            torch.cuda.synchronize(dev)
+        for L in lanes:
+            L["ctx"].set_profiling(False)
+        phases = read_all()
     # optional: the whole step captured once as a HIP graph and replayed (every kernel still
     # runs every step; the graph only removes host launch cost).  fia_prepare_for (large k)
     # decides the cache size on the host, so those configs run eagerly.
@@ -705,10 +765,11 @@ def main():
             compute()
         torch.cuda.synchronize(dev)
 
-    # the step's dominant phase (instrumented steps above) is priced by the roofline; its
-    # launches and the scoring kernel's are timed by HIP events over the timed region
+    # --full: the step's dominant phase (instrumented steps above) is priced by the roofline; its
+    # launches and the scoring kernel's are timed by HIP events over the timed region.  A plain
+    # run prices the scoring kernel (the metric's HBM roofline) from its event pair alone.
     per_step = {p: v[0] / n_instr for p, v in phases.items()}
-    dom = max(("prepare", "solve", "score"), key=lambda p: per_step.get(p, 0.0))
+    dom = max(("prepare", "solve", "score"), key=lambda p: per_step.get(p, 0.0)) if args.full else "score"
     if not args.no_timed_events:
         for L in lanes:
             L["ctx"].set_profiling(True, phases=tuple(sorted({"score", dom})))
@@ -731,6 +792,9 @@ def main():
     for L in lanes:
         L["ctx"].set_profiling(False)
     timed = read_all()          # scoring kernel duration over the timed region
+    if args.dump_outputs and rank == 0:
+        last = lanes[0] if graph is not None else lanes[(step_no[0] - 1) % len(lanes)]
+        dump_outputs(args.dump_outputs, last, last["batches"][-1], Q, K, D)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=gdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -761,7 +825,8 @@ def main():
     deg_u = np.bincount(tu, minlength=U).astype(np.float64)
     deg_i = np.bincount(ti, minlength=I).astype(np.float64)
     comp = compulsory_bytes(cfg, qu_np, qi_np, deg_u, deg_i, bounds)
-    achieved = traffic / (score_ms * 1e-3) / 1e9 if traffic else None
+    # (no event time at all: a plain run with --no-timed-events)
+    achieved = traffic / (score_ms * 1e-3) / 1e9 if traffic and score_ms > 0 else None
     score_hbm = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                  "frac": achieved / HBM_PEAK_GBS if achieved is not None else None, "traffic": traffic,
                  "compulsory_bytes": comp, "traffic_over_compulsory": traffic / comp if traffic else None,
@@ -769,8 +834,9 @@ def main():
                  "source": ("rocprofv3 PMC (FETCH_SIZE x 2 + WRITE_SIZE) per launch, %s" % os.path.relpath(
                      args.traffic_json, ROOT)) if traffic else "no PMC traffic recorded for this config/kernel",
                  "algorithmic": {"model": "SURVEY.md 8d (gathered rows counted once per query)",
-                                 "bytes_per_launch": alg_bytes, "gbs": alg_bytes / (score_ms * 1e-3) / 1e9}}
-    if len(lanes) > 1:
+                                 "bytes_per_launch": alg_bytes,
+                                 "gbs": alg_bytes / (score_ms * 1e-3) / 1e9 if score_ms > 0 else None}}
+    if args.full and len(lanes) > 1:
         # batches in flight share the GPU, so the timed-region launch is longer than the
         # kernel alone: the same bytes over the instrumented (one step at a time) launches too
         iso = phases.get("score", (0.0, 0))
@@ -844,10 +910,11 @@ def main():
                    "dist_backend": backend if world > 1 else None,
                    "parallelism": "dp%d (query shards, top-K all_gather)" % world},
         "roofline": roofline,
-        "phases_ms_per_step": {p: v[0] / n_instr for p, v in phases.items()},
-        "phases_ms_per_launch": {p: (v[0] / max(v[1], 1)) for p, v in phases.items()},
         "index_build_s": index_s,
     }
+    if args.full:
+        out["phases_ms_per_step"] = {p: v[0] / n_instr for p, v in phases.items()}
+        out["phases_ms_per_launch"] = {p: (v[0] / max(v[1], 1)) for p, v in phases.items()}
     if repair:
         out["config"]["rank0_requery"] = repair
     if cpu is not None:

@@ -12,6 +12,6 @@ mkdir -p gpurun_out/abq
 for lib in "${libs[@]}"; do
   if [ "$lib" = "-" ]; then unset FIA_LIB; else export FIA_LIB=$(realpath "$lib"); fi
   log=gpurun_out/abq/$(basename "$lib" .so)_$cfg.log
-  timeout -k 10 300 python bench.py --config $cfg --no-cpu-baseline "$@" > "$log" 2>&1 || { echo "bench $lib failed"; tail -5 "$log"; exit 1; }
+  timeout -k 10 300 python bench.py --config $cfg --full --no-cpu-baseline "$@" > "$log" 2>&1 || { echo "bench $lib failed"; tail -5 "$log"; exit 1; }
   tail -1 "$log" | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('%-36s' % '$lib', round(d['value']), round(d['ms_per_step'], 4), {k: round(v, 4) for k, v in d['phases_ms_per_launch'].items()}, 'score_ev', round(d['roofline'].get('kernel_ms', 0) if d['roofline'].get('phase') == 'score' else d['roofline']['score_hbm']['kernel_ms'], 4))"
 done

@@ -17,7 +17,7 @@ step() {
   echo "step $n exit $rc" | tee -a "$out/steps.log"
   [ $rc -eq 0 ] || exit $rc
 }
-step bench 900 python bench.py --config "$cfg" --no-cpu-baseline "$@"
+step bench 900 python bench.py --config "$cfg" --full --no-cpu-baseline "$@"
 step stats 600 rocprofv3 --kernel-trace --stats -d "$out/stats" -o run --output-format csv -- \
   python3 bench.py --config "$cfg" --no-cpu-baseline "$@"
 [ "${PMC:-1}" = "1" ] || exit 0

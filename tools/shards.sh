@@ -7,7 +7,7 @@ export TMPDIR=/tmp FIA_SYNTH_CACHE=/tmp/fia_synth
 cfg=$1; S=$2; steps=${3:-3}
 mkdir -p gpurun_out/shards
 for r in $(seq 0 $((S - 1))); do
-  timeout -k 10 600 python bench.py --config "$cfg" --shard-of "$S" --shard-index "$r" --no-cpu-baseline \
+  timeout -k 10 600 python bench.py --config "$cfg" --shard-of "$S" --shard-index "$r" --full --no-cpu-baseline \
       --steps "$steps" --warmup 1 --spinup-seconds 5 > "gpurun_out/shards/${cfg}_$r.log" 2>&1
   rc=$?
   echo "shard $r exit $rc"
