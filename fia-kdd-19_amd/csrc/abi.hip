@@ -447,6 +447,18 @@ static int query_batch_common(fia_ctx* c, int64_t Q, const int32_t* qu, const in
     if (Q > 0 && (!qu || !qi || !offsets)) return fail(c, FIA_ERR_INVALID, "null query array");
     if (K > 0 && (!topk_pos || !topk_idx || !topk_val)) return fail(c, FIA_ERR_INVALID, "null top-K output");
     if (Q == 0) return FIA_OK;
+    // MF k in {32, 64}, K <= 1 (k_score_mf_mfma) keeps its output offsets and candidate slots
+    // in 32 bits.  A stored element is el = ob0 + idx with ob0 the run's first element and
+    // idx < the run's length, computed modulo 2^32 in a uint32_t: every stored el is
+    // < total_rel, so total_rel <= 2^32 is exact.  A candidate slot is an int32_t: slot base +
+    // chunk of the list, below the batch's chunk count sum_q ceil(|R_u| / kChunk) +
+    // ceil(|C_i| / kChunk) <= 2 Q + total_rel / kChunk, which must stay <= 2^31 - 1.
+    if (c->p.model == FIA_MODEL_MF && (c->p.k == 32 || c->p.k == 64) && K <= 1) {
+      if (total_rel > FIA_MFMA_MAX_TOTAL_REL)
+        return fail(c, FIA_ERR_INVALID, "total_rel > 2^32: split the batch (MF k in {32, 64}, K <= 1)");
+      if (2 * Q + total_rel / fia::kChunk > FIA_MFMA_MAX_CHUNKS)
+        return fail(c, FIA_ERR_INVALID, "more than 2^31 - 1 list chunks: split the batch (MF k in {32, 64}, K <= 1)");
+    }
     DeviceGuard g(c->device);
     if (int rc = enter_stream(c, as_stream(stream), "fia_query_batch"); rc != FIA_OK) return rc;
     // (small k joins the pending Gram pass right before its solve, after the query scans)

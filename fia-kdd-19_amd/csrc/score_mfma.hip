@@ -7,9 +7,11 @@
 // pair are one 16x16 tile
 //   D = X . G^T      (v_mfma_f64_16x16x4_f64, K/4 slices of 4 coordinates)
 // with A rows = the block's 16 queries' x (side block, k coordinates).  The rating's residual
-// e_n = r-hat_n - y_n comes from the prepare's list-ordered residuals (k_lres_mf, read with the
-// list entries; round 6: row 15 of A was the entity's embedding, D[15][n] the residual's dot --
-// 1/16 of the MFMAs and the other side's bias gather per tile).  Slice s pairs coordinate (K/4) kk + s of lane group
+// e_n = r-hat_n - y_n comes from the prepare's list-ordered residuals (written by the Gram
+// pass k_gram_mf_mfma for every list position of a cached entity, read with the list entries;
+// before round 6 row 15 of A was the entity's embedding and D[15][n] the residual's dot --
+// 1/16 of the MFMAs and the other side's bias gather per tile -- a scheme round 6 removed).
+// Slice s pairs coordinate (K/4) kk + s of lane group
 // kk = l >> 4: every lane loads K/4 CONTIGUOUS coordinates of its query's x (once per work
 // item) and of its rating's gathered row (per tile, 16-B loads).  MI355X runs f64 MFMA and f64
 // VALU on the same units (tools/mb_f64.hip: their times add), so the epilogue keeps f64 work
@@ -157,8 +159,9 @@ __global__ __launch_bounds__(kScoreThreads) __attribute__((amdgpu_waves_per_eu(3
     // this wave's LDS rows (read back per k-slice pair: registers bound the occupancy)
     double a[KS];
     // per D row r (query m = kk + 4 r): influence = fma(e * al, D + xb, be)
-    // (32-bit element offsets and candidate slots: a batch holds < 2^29 related ratings and
-    // fewer chunks, fia_query_batch; registers are what bounds this kernel's occupancy)
+    // (32-bit element offsets and candidate slots: fia_query_batch refuses a batch of more
+    // than 2^32 related ratings or 2^31 - 1 chunks; registers are what bounds this kernel's
+    // occupancy)
     bool qv[4] = {false, false, false, false};
     if (nq > 0) {
       {
@@ -189,7 +192,7 @@ __global__ __launch_bounds__(kScoreThreads) __attribute__((amdgpu_waves_per_eu(3
         const int32_t dup_other = (int32_t)R[4 + sd * M::SB + 2 * K + 2];
         const longlong2* __restrict__ qb = reinterpret_cast<const longlong2*>(qbase + 4 * (int64_t)qr[r]);
         const longlong2 q01 = qb[0], q23 = qb[1];          // {out base user, item}, {slot base user, item}
-        // the row's output run starts at element ob0 (< 2^29: fia_query_batch's batch bound)
+        // the row's output run starts at element ob0 (< 2^32: fia_query_batch's batch bound)
         const uint32_t ob0 = (uint32_t)((sd ? q01.y : q01.x) + p0);
         if (cn == 0) {
           double* __restrict__ w4 = sQ[wave][kk + 4 * r];

@@ -146,7 +146,15 @@ int fia_related(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const 
  * position (topk_pos), train row (topk_idx) and signed influence (topk_val),
  * device arrays [Q*K]; unused slots hold -1 / NaN (n_q < K).
  * total_rel must equal offsets[Q].  Queries with n_q = 0 produce no ratings
- * and a NaN x (TF's mean over an empty batch). */
+ * and a NaN x (TF's mean over an empty batch).
+ * Batch limit, MF k in {32, 64} with K <= 1 (the matrix-core scoring kernel keeps 32-bit
+ * element offsets and candidate slots): total_rel <= FIA_MFMA_MAX_TOTAL_REL (2^32) and
+ * 2 * num_queries + total_rel / 256 <= FIA_MFMA_MAX_CHUNKS (2^31 - 1); a larger batch is
+ * refused with FIA_ERR_INVALID before anything is reserved or launched -- split it.
+ * rel_idx / influence need only their types' natural alignment (4 B / 8 B): every scoring
+ * kernel stores per element, whatever the base pointers' offset within a cache line. */
+#define FIA_MFMA_MAX_TOTAL_REL (1LL << 32)
+#define FIA_MFMA_MAX_CHUNKS ((1LL << 31) - 1)
 int fia_query_batch(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item,
                     const int64_t* offsets, int64_t total_rel,
                     int32_t* rel_idx, double* influence, double* x_out,
