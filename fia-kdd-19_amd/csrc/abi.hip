@@ -494,6 +494,43 @@ int fia_query_batch_x(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
                             topk_val, stream, x_in);
 }
 
+int fia_score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const double* x,
+                         const int64_t* cand_offsets, int64_t total_cand, const int32_t* cand_user,
+                         const int32_t* cand_item, const float* cand_rating, double* influence, int K,
+                         int64_t* topk_pos, double* topk_val, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    if (!c->p.valid || !c->idx.valid) return fail(c, FIA_ERR_STATE, "params/index missing");
+    if (!c->prepared) return fail(c, FIA_ERR_STATE, "fia_prepare has not been called since params/index changed");
+    if (Q < 0 || Q >= (1LL << 31)) return fail(c, FIA_ERR_INVALID, "num_queries out of range");
+    if (total_cand < 0) return fail(c, FIA_ERR_INVALID, "total_cand < 0");
+    // a candidate's position inside its query's list is kept in 32 bits by the top-K selection
+    // (element offsets into the candidate and influence arrays are 64-bit)
+    if (total_cand > FIA_CAND_MAX_TOTAL)
+      return fail(c, FIA_ERR_INVALID, "total_cand > 2^31 - 1: split the batch");
+    if (K < 0 || K > FIA_MAX_TOPK) return fail(c, FIA_ERR_INVALID, "K must be in [0, FIA_MAX_TOPK]");
+    if (Q > 0 && (!qu || !qi || !x || !cand_offsets)) return fail(c, FIA_ERR_INVALID, "null query array");
+    if (total_cand > 0 && (!cand_user || !cand_item || !cand_rating))
+      return fail(c, FIA_ERR_INVALID, "null candidate array");
+    if (K > 0 && (!topk_pos || !topk_val)) return fail(c, FIA_ERR_INVALID, "null top-K output");
+    if (Q == 0) return FIA_OK;
+    if (!fia::model_supported(c->p.model, c->p.k)) return fail(c, FIA_ERR_UNSUPPORTED, "model/k not supported");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_score_candidates"); rc != FIA_OK) return rc;
+    // of what a pending small-k Gram pass writes, only the NCF layer-1 rows are read here (its
+    // first kernels: l1_ev; once that is joined on this stream nothing else is waited for)
+    if (c->p.model == FIA_MODEL_NCF && c->l1_pending)
+      if (hipError_t es = fia::join_l1(c, s); es != hipSuccess) return hip_fail(c, es, "fia_score_candidates");
+    bool unsup = false;
+    hipError_t e = fia::score_candidates(c, Q, qu, qi, x, cand_offsets, total_cand, cand_user, cand_item,
+                                         cand_rating, influence, K, topk_pos, topk_val, s, unsup);
+    if (unsup) return fail(c, FIA_ERR_UNSUPPORTED, "model/k not supported");
+    if (e != hipSuccess) return hip_fail(c, e, "fia_score_candidates");
+    return FIA_OK;
+  })
+}
+
 int fia_set_profiling(fia_ctx* c, int phase_mask) {
   if (!c) return FIA_ERR_INVALID;
   c->profiling = (unsigned)phase_mask & ((1u << FIA_NUM_PHASES) - 1u);

@@ -374,6 +374,14 @@ hipError_t launch_topk_merge(fia_ctx* c, int64_t Q, const int32_t* qu, const int
                              int64_t* topk_pos, int64_t* topk_idx, double* topk_val, hipStream_t s,
                              int64_t max_chunks);
 
+// fia_score_candidates (score_cand.hip): hypothetical ratings scored from the parameter tables
+// (and the dense NCF layer-1 rows c->l1), x read from global memory in the reference order;
+// scratch: c->rec, c->cand_pos, c->cand_val
+hipError_t score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const double* x,
+                            const int64_t* cand_offsets, int64_t total_cand, const int32_t* cand_user,
+                            const int32_t* cand_item, const float* cand_rating, double* influence, int K,
+                            int64_t* topk_pos, double* topk_val, hipStream_t s, bool& unsupported);
+
 // phase event helpers (no-ops unless profiling)
 void phase_begin(fia_ctx* c, int phase, hipStream_t s);
 void phase_end(fia_ctx* c, int phase, hipStream_t s);

@@ -38,6 +38,7 @@ SIGNATURES = {
     "fia_related": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _P]),
     "fia_query_batch": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
     "fia_query_batch_x": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
+    "fia_score_candidates": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "fia_num_params": (ctypes.c_int, [_P]),
     "fia_set_profiling": (ctypes.c_int, [_P, ctypes.c_int]),
     "fia_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I64)]),
@@ -195,6 +196,44 @@ class Context(object):
                                         _ptr(x_in), _ptr(rel_idx), _ptr(influence), int(K), _ptr(topk_pos),
                                         _ptr(topk_idx), _ptr(topk_val), _stream())
         self._check(rc, "fia_query_batch_x")
+
+    def score_candidates(self, qu, qi, x, cand_offsets, total, cand_user, cand_item, cand_rating,
+                         influence=None, K=0, topk_pos=None, topk_val=None):
+        """fia_score_candidates: the influence of hypothetical ratings (cand_user, cand_item,
+        cand_rating), candidates cand_offsets[q]:cand_offsets[q+1] belonging to query q, given
+        the queries' inverse HVPs x (float64 cuda tensor [Q * D], reference theta order)."""
+        import torch
+        for t, name in ((qu, "qu"), (qi, "qi"), (cand_user, "cand_user"), (cand_item, "cand_item")):
+            self._need_int32(t, name)
+        if x.dtype != torch.float64 or not x.is_contiguous() or not x.is_cuda:
+            raise TypeError("x must be a contiguous torch.float64 device (cuda) tensor")
+        if x.numel() < qu.numel() * self.num_params():
+            raise ValueError("x holds %d values, %d queries need %d" % (
+                x.numel(), qu.numel(), qu.numel() * self.num_params()))
+        if cand_rating.dtype != torch.float32:
+            raise TypeError("cand_rating must be a torch.float32 tensor (got %s)" % cand_rating.dtype)
+        if cand_offsets.dtype != torch.int64 or cand_offsets.numel() != qu.numel() + 1:
+            raise TypeError("cand_offsets must be a torch.int64 tensor of Q + 1 values")
+        if influence is not None and influence.dtype != torch.float64:
+            raise TypeError("influence must be a torch.float64 tensor")
+        if topk_pos is not None and topk_pos.dtype != torch.int64:
+            raise TypeError("topk_pos must be a torch.int64 tensor")
+        if topk_val is not None and topk_val.dtype != torch.float64:
+            raise TypeError("topk_val must be a torch.float64 tensor")
+        for t, name in ((cand_offsets, "cand_offsets"), (cand_user, "cand_user"), (cand_item, "cand_item"),
+                        (cand_rating, "cand_rating"), (influence, "influence"), (topk_pos, "topk_pos"),
+                        (topk_val, "topk_val")):
+            if t is not None and not (t.is_cuda and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous device (cuda) tensor" % name)
+        if min(cand_user.numel(), cand_item.numel(), cand_rating.numel()) < total or (
+                influence is not None and influence.numel() < total):
+            raise ValueError("candidate arrays hold fewer than total = %d values" % total)
+        if K and (topk_pos is None or topk_val is None or min(topk_pos.numel(), topk_val.numel()) < qu.numel() * K):
+            raise ValueError("top-K outputs must hold Q * K values")
+        rc = self.lib.fia_score_candidates(self.h, qu.numel(), _ptr(qu), _ptr(qi), _ptr(x), _ptr(cand_offsets),
+                                           int(total), _ptr(cand_user), _ptr(cand_item), _ptr(cand_rating),
+                                           _ptr(influence), int(K), _ptr(topk_pos), _ptr(topk_val), _stream())
+        self._check(rc, "fia_score_candidates")
 
     # ---- profiling ----
     def set_profiling(self, on, phases=None):

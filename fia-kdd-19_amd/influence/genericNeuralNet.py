@@ -383,6 +383,88 @@ class GenericNeuralNet(object):
             out["topk_val"] = tv[:Q * K].cpu().numpy().reshape(Q, K)
         return out
 
+    def _checked_candidates(self, n_queries, cand_offsets, X, Y):
+        """Host validation of a candidate batch (no GPU call): returns (offsets int64[Q+1],
+        users int32[M], items int32[M], ratings float32[M]) or raises ValueError."""
+        off = np.asarray(cand_offsets)
+        if off.ndim != 1 or off.size != n_queries + 1 or off.dtype.kind not in "iu":
+            raise ValueError("cand_offsets must be an integer array of len(test_indices) + 1 values")
+        off = np.ascontiguousarray(off, np.int64)
+        X = np.asarray(X)
+        Y = np.asarray(Y)
+        if X.ndim != 2 or X.shape[1] != 2:
+            raise ValueError("X must have shape [M, 2] (user, item)")
+        if Y.ndim != 1 or Y.shape[0] != X.shape[0]:
+            raise ValueError("X and Y must have the same length.")
+        m = X.shape[0]
+        if off[0] != 0 or off[-1] != m or (np.diff(off) < 0).any():
+            raise ValueError("cand_offsets must start at 0, never decrease and end at len(Y) = %d" % m)
+        if m and X.dtype.kind == "f" and not (np.isfinite(X).all() and (X == np.floor(X)).all()):
+            raise ValueError("candidate ids must be integers")
+        users = X[:, 0].astype(np.int64)
+        items = X[:, 1].astype(np.int64)
+        if m and (users.min() < 0 or users.max() >= self.num_users or items.min() < 0 or
+                  items.max() >= self.num_items):
+            raise ValueError("candidate ids must lie in [0, %d) x [0, %d)" % (self.num_users, self.num_items))
+        return (off, np.ascontiguousarray(users, np.int32), np.ascontiguousarray(items, np.int32),
+                np.ascontiguousarray(Y, np.float32))
+
+    def get_candidate_influence_batch(self, test_indices, cand_offsets, X, Y, K=0, full=True, inverse_hvp=None):
+        """Influence of HYPOTHETICAL ratings on the predictions of many test ratings (one
+        fia_score_candidates call): candidates cand_offsets[q]:cand_offsets[q+1] -- rows of
+        X [M, 2] (user, item) with ratings Y [M] -- belong to test rating test_indices[q].  A
+        candidate need not be a train row and need not share the query's user or item:
+
+            influence_c = x_q . (2 (r-hat(a, b) - y) d r-hat(a, b)/d theta_t + wd M theta_t) / n_q
+
+        with n_q the query's related-set size, so a candidate equal to a related train row gets
+        that row's influence (include/fia.h).  x_q comes from one fia_query_batch call (no
+        per-rating vectors), or from inverse_hvp (float64 [Q, D], reference theta order) as in
+        get_influence_batch.  Shapes, offsets and id ranges are checked on the host (ValueError)
+        before any GPU call.  Returns dict(cand_offsets, influence, x, topk_pos, topk_val) as
+        numpy arrays (influence only with full, top-K only with K: positions inside each query's
+        candidate list, -1 / NaN where the list is shorter than K)."""
+        off, cu, ci, cy = self._checked_candidates(len(test_indices), cand_offsets, X, Y)
+        if not 0 <= int(K) <= _lib.FIA_MAX_TOPK:
+            raise ValueError("K must be in [0, %d]" % _lib.FIA_MAX_TOPK)
+        import torch
+        K = int(K)
+        qu, qi = self._query_tensors(test_indices)
+        Q = qu.numel()
+        dev = self.ctx.torch_device
+        D = self.ctx.num_params()
+        # (the count also rejects query ids out of range and queries outside a prepare_for cover)
+        offsets, total = self.ctx.count_related(qu, qi)
+        if inverse_hvp is not None:
+            xin = np.ascontiguousarray(np.asarray(inverse_hvp, np.float64).reshape(-1))
+            if xin.size != Q * D:
+                raise ValueError("inverse_hvp must hold %d x %d values" % (Q, D))
+            x = torch.from_numpy(xin).to(dev)
+        else:
+            x = torch.empty(max(Q * D, 1), dtype=torch.float64, device=dev)
+            self.ctx.query_batch(qu, qi, offsets, total, None, None, x, 0, None, None, None)
+        m = cy.size
+        d_off = torch.from_numpy(off).to(dev)
+        d_cu = torch.from_numpy(cu).to(dev) if m else torch.empty(1, dtype=torch.int32, device=dev)
+        d_ci = torch.from_numpy(ci).to(dev) if m else torch.empty(1, dtype=torch.int32, device=dev)
+        d_cy = torch.from_numpy(cy).to(dev) if m else torch.empty(1, dtype=torch.float32, device=dev)
+        infl = torch.empty(max(m, 1), dtype=torch.float64, device=dev) if full else None
+        tp = torch.empty(max(Q * K, 1), dtype=torch.int64, device=dev) if K else None
+        tv = torch.empty(max(Q * K, 1), dtype=torch.float64, device=dev) if K else None
+        self.ctx.score_candidates(qu, qi, x, d_off, m, d_cu, d_ci, d_cy, infl, K, tp, tv)
+        out = dict(cand_offsets=off, x=x[:Q * D].cpu().numpy().reshape(Q, D))
+        if full:
+            out["influence"] = infl[:m].cpu().numpy()
+        if K:
+            out["topk_pos"] = tp[:Q * K].cpu().numpy().reshape(Q, K)
+            out["topk_val"] = tv[:Q * K].cpu().numpy().reshape(Q, K)
+        return out
+
+    def _score_one_query_candidates(self, test_index, x, X, Y):
+        off = np.array([0, len(Y)], np.int64)
+        return self.get_candidate_influence_batch([test_index], off, X, Y, K=0, full=True,
+                                                  inverse_hvp=x)["influence"]
+
     def get_influence_on_test_loss(self, test_indices, train_idx, approx_type="cg", approx_params=None,
                                    force_refresh=True, test_description=None, loss_type="normal_loss",
                                    X=None, Y=None):
@@ -390,18 +472,24 @@ class GenericNeuralNet(object):
         removed (mf:164-251, ncf:193-280).  Returns float64[n] aligned with
         self.train_indices_of_test_case.
 
+        Phantom points (train_idx None with X [M, 2] and Y [M] given, mf:228-235): the call
+        runs as usual up to and including the inverse HVP (cache file, save_inverse_hvp and the
+        side-effect attributes alike) and returns float64[len(Y)], the influence of each
+        hypothetical rating (X[c, 0], X[c, 1], Y[c]) as get_candidate_influence_batch defines
+        it -- divided by the query's related-set size, not by num_train_examples.
+
         Differences from the reference, by design: the inverse HVP is the exact fp64
         solve (the reference's fmin_ncg approximates it, mf:424-431); errors raise
-        ValueError (the reference raises tuples, mf:173-177); the phantom-point branch
-        (train_idx None, mf:228-235) is shape-inconsistent in the reference and raises
-        NotImplementedError here."""
-        if train_idx is None:
+        ValueError (the reference raises tuples, mf:173-177); the reference's own
+        phantom-point branch is shape-inconsistent (it dots the restricted inverse HVP with a
+        full-parameter gradient) and cannot run."""
+        phantom = train_idx is None
+        if phantom:
             if X is None or Y is None:
                 raise ValueError("X and Y must be specified if using phantom points.")
             if X.shape[0] != len(Y):
                 raise ValueError("X and Y must have the same length.")
-            raise NotImplementedError("phantom points (train_idx=None) are not supported")
-        if X is not None or Y is not None:
+        elif X is not None or Y is not None:
             raise ValueError("X and Y cannot be specified if train_idx is specified.")
         if approx_type == "lissa":
             # gnn:503-508 dispatches 'lissa' to get_inverse_hvp_lissa (gnn:511-544); this
@@ -413,6 +501,8 @@ class GenericNeuralNet(object):
         if loss_type != "normal_loss":
             raise ValueError("Loss must be normal")
         assert len(test_indices) == 1
+        if phantom:     # shapes and id ranges, on the host, before any GPU call
+            self._checked_candidates(1, np.array([0, len(Y)], np.int64), X, Y)
         t0 = time.time()
         self.test_index = test_indices[0]
         self.test_u, self.test_i = self._test_pair(self.test_index)
@@ -452,6 +542,13 @@ class GenericNeuralNet(object):
         self.inverse_hvp = self._split_theta(x)
         if self.save_inverse_hvp and cached is None and not unusable:
             np.savez(fname, inverse_hvp=x)
+        if phantom:
+            # the hypothetical ratings scored with the same inverse HVP (fia_score_candidates;
+            # its kernels add to the 'score' phase of the timers)
+            infl, more = self.ctx.profiled_call(lambda: self._score_one_query_candidates(self.test_index, x, X, Y))
+            phases = {p: (phases[p][0] + more[p][0], phases[p][1] + more[p][1]) for p in phases}
+            self.last_timing = rq2_timing(phases, infl.size, time.time() - t0, log=print if self.verbose else None)
+            return infl
         self.last_timing = rq2_timing(phases, res["influence"].size, time.time() - t0,
                                       log=print if self.verbose else None)
         return res["influence"]

@@ -20,6 +20,9 @@
  *     (mf:237-246, ncf:266-274)
  *   top-K of experiments.test_retraining                 fia_query_batch (top-K)
  *     (experiments.py:46-48)
+ *   phantom-point branch of get_influence_on_test_loss   fia_score_candidates
+ *     (train_idx None, X / Y given: mf:228-235, and the
+ *      same branch of NCF.py)
  *
  * Conventions
  *   - All array arguments are DEVICE pointers owned by the caller (PyTorch).
@@ -171,6 +174,50 @@ int fia_query_batch_x(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, 
                       const int64_t* offsets, int64_t total_rel, const double* x_in,
                       int32_t* rel_idx, double* influence,
                       int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val, void* stream);
+
+/* Influence of HYPOTHETICAL ratings on each query's prediction: the reference's phantom-point
+ * branch (train_idx None, X / Y given: matrix_factorization.py:228-235, NCF.py likewise), which
+ * cannot run there (it dots the restricted inverse HVP with a full-parameter gradient) and is
+ * defined here.  Query q = (q_user[q], q_item[q]) has n_q = |R_u| + |C_i| from the built index
+ * (read on the device: no related offsets are passed) and the inverse HVP x_q = x[q*D .. ) in the
+ * reference theta order (fia_query_batch's x_out, or any given vector).  Its candidates are
+ * c in [cand_offsets[q], cand_offsets[q+1]): (a, b, y) = (cand_user[c], cand_item[c],
+ * cand_rating[c]); a candidate need not be a train row and need not share u or i.
+ *   e_c    = r-hat(a, b) - y                         (current parameters, fp64)
+ *   g_c    = d r-hat(a, b) / d theta_t               user-side blocks zero unless a == u,
+ *                                                    item-side blocks zero unless b == i
+ *   influence[c] = x_q . (2 e_c g_c + wd * M * theta_t) / n_q
+ * with M = [1]*2k + [0, 0] (MF) or all ones (NCF): the expression fia_query_batch scores a
+ * related rating with, the train row replaced by the candidate.  The divisor is the query's n_q
+ * (not the reference branch's num_train_examples), so a candidate equal to a related train row
+ * (u_j, i_j, y_j) gets that row's influence.  A candidate sharing neither u nor i scores the
+ * constant x_q . (wd * M * theta_t) / n_q; n_q = 0 gives NaN (x is NaN); duplicates are allowed
+ * and score identically.  A candidate id outside [0, num_users) x [0, num_items) is never used
+ * as an index: that candidate scores NaN.
+ * topk (K in [0, FIA_MAX_TOPK]; 0 = off): per query the K candidates of largest |influence| in
+ * fia_query_batch's order (ties: lower position first, NaN last) as position inside the query's
+ * candidate list (topk_pos) and signed influence (topk_val), device arrays [Q*K]; unused slots
+ * hold -1 / NaN.  There is no topk_idx: a candidate has no train row.  influence may be NULL
+ * (with K > 0 only the top-K is written).  The result does not depend on how the lists are cut
+ * into work items.
+ * Needs params, index and a prepare (else FIA_ERR_STATE).  After fia_prepare_for the QUERIES
+ * must be covered (their x came from a covered query); candidate entities may be any in-range
+ * id, and the results are bitwise those after fia_prepare.  Ordered on `stream`, no host
+ * synchronisation; of a pending small-k Gram pass it waits only for the NCF layer-1 rows.
+ * cand_offsets[0] == 0, non-decreasing, cand_offsets[Q] == total_cand.
+ * Batch limit: total_cand <= FIA_CAND_MAX_TOTAL (2^31 - 1; the top-K selection keeps a
+ * candidate's position in 32 bits, element offsets are 64-bit): a larger batch is refused with
+ * FIA_ERR_INVALID before anything is reserved or launched -- split it.  num_queries == 0
+ * returns FIA_OK and launches nothing. */
+#define FIA_CAND_MAX_TOTAL ((1LL << 31) - 1)
+int fia_score_candidates(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item,
+                         const double* x,                 /* device [Q*D], reference theta order          */
+                         const int64_t* cand_offsets,     /* device [Q+1], cand_offsets[0] == 0           */
+                         int64_t total_cand,              /* == cand_offsets[Q]                           */
+                         const int32_t* cand_user, const int32_t* cand_item, const float* cand_rating,
+                         double* influence,               /* device [total_cand], nullable                */
+                         int K, int64_t* topk_pos, double* topk_val,   /* [Q*K], K in [0, FIA_MAX_TOPK]   */
+                         void* stream);
 
 /* Number of restricted parameters D of the registered model (0 if none). */
 int fia_num_params(const fia_ctx* ctx);
