@@ -343,7 +343,7 @@ def test_prepare_for_subset(model, k, tmp_path):
 
 @pytest.mark.parametrize("model,k", [("MF", 16), ("NCF", 8), ("MF", 32), ("MF", 64)])
 def test_many_queries_scan_windows(model, k, tmp_path):
-    """40,000 queries (157 scan tiles of 256: the decoupled look-back walks more than one
+    """40,000 queries (79 scan tiles of 512: the decoupled look-back walks more than one
     64-tile window) with repeated users and items: offsets = deg(u) + deg(i) exactly, the
     related lists and top-K are consistent, and a sample matches the oracle."""
     from oracle import fia_oracle as fo
