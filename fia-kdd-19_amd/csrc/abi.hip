@@ -240,7 +240,8 @@ int fia_destroy(fia_ctx* c) {
                            &c->flag,   &c->nch,    &c->coupled,  &c->idx.pkey,  &c->idx.pcnt, &c->idx.psum,
                            &c->gcnt,   &c->gstart, &c->grank,    &c->gq,        &c->qbase,    &c->gscan,
                            &c->wstart, &c->witems, &c->resid,  &c->qwork,  &c->xb,       &c->syslist,
-                           &c->cpllist, &c->lscr, &c->mark, &c->d1tab, &c->slices, &c->wfrag};
+                           &c->cpllist, &c->lscr, &c->mark, &c->d1tab, &c->slices, &c->wfrag,
+                           &c->tkeys, &c->tvals, &c->tagg, &c->tslot, &c->tword, &c->tsort};
     for (auto* b : bufs) rel(*b);
     if (can_free) (void)hipStreamSynchronize(ds);   // the stream-ordered frees complete
     if (c->aux && !capturing) (void)hipStreamDestroy(c->aux);
@@ -527,6 +528,34 @@ int fia_score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t
                                          cand_rating, influence, K, topk_pos, topk_val, s, unsup);
     if (unsup) return fail(c, FIA_ERR_UNSUPPORTED, "model/k not supported");
     if (e != hipSuccess) return hip_fail(c, e, "fia_score_candidates");
+    return FIA_OK;
+  })
+}
+
+int fia_total_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const double* x, double* total,
+                        int32_t* count, int K, int64_t* topk_idx, double* topk_val, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    // the batch bound comes first: nothing of an oversized batch is looked at
+    if (Q < 0 || Q > FIA_TOTAL_MAX_QUERIES)
+      return fail(c, FIA_ERR_INVALID, "num_queries out of range [0, 2^30]: split the batch (totals add)");
+    if (!c->p.valid || !c->idx.valid) return fail(c, FIA_ERR_STATE, "params/index missing");
+    if (!c->prepared) return fail(c, FIA_ERR_STATE, "fia_prepare has not been called since params/index changed");
+    if (K < 0 || K > FIA_MAX_TOPK) return fail(c, FIA_ERR_INVALID, "K must be in [0, FIA_MAX_TOPK]");
+    if (K > 0 && (!topk_idx || !topk_val)) return fail(c, FIA_ERR_INVALID, "null top-K output");
+    if (!total && !count && K == 0) return fail(c, FIA_ERR_INVALID, "no output requested (total, count, top-K)");
+    if (Q > 0 && (!qu || !qi || !x)) return fail(c, FIA_ERR_INVALID, "null query array");
+    if (!fia::model_supported(c->p.model, c->p.k)) return fail(c, FIA_ERR_UNSUPPORTED, "model/k not supported");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_total_influence"); rc != FIA_OK) return rc;
+    // as fia_score_candidates: of a pending small-k Gram pass only the NCF layer-1 rows are read
+    if (c->p.model == FIA_MODEL_NCF && c->l1_pending)
+      if (hipError_t es = fia::join_l1(c, s); es != hipSuccess) return hip_fail(c, es, "fia_total_influence");
+    bool unsup = false;
+    hipError_t e = fia::total_influence(c, Q, qu, qi, x, total, count, K, topk_idx, topk_val, s, unsup);
+    if (unsup) return fail(c, FIA_ERR_UNSUPPORTED, "model/k not supported");
+    if (e != hipSuccess) return hip_fail(c, e, "fia_total_influence");
     return FIA_OK;
   })
 }

@@ -230,6 +230,9 @@ struct fia_ctx {
   fia::DevBuf gscan;      // k_group_scan tile words + counters (left zero by every launch)
   fia::DevBuf witems;     // int32 [3 * max items] {global entity, list chunk, query block}
   fia::DevBuf d1tab;      // NCF k <= 16: d1 per z2 ReLU mask [2^(k/2)][k] (fp64)
+  // fia_total_influence (total.hip), per batch: sort keys / queries (in, out) of the 2Q (entity,
+  // query) pairs, per-group aggregates, entity -> group, per-query / per-group words, sort scratch
+  fia::DevBuf tkeys, tvals, tagg, tslot, tword, tsort;
   // large-k path (bigk.hip): per-list-position entity, per-train-row residual / NCF backward
   // vectors, per-query Hessian inputs and solutions, solve lists and LDL^T scratch
   fia::DevBuf self[2];    // int32 [N] entity owning list position p of side s
@@ -381,6 +384,13 @@ hipError_t score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int3
                             const int64_t* cand_offsets, int64_t total_cand, const int32_t* cand_user,
                             const int32_t* cand_item, const float* cand_rating, double* influence, int K,
                             int64_t* topk_pos, double* topk_val, hipStream_t s, bool& unsupported);
+
+// fia_total_influence (total.hip): the scatter-add of fia_query_batch_x's influence by train
+// row, computed from per-entity aggregates of the queries; scratch: c->rec, c->cand_pos,
+// c->cand_val and the t* buffers
+hipError_t total_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const double* x,
+                           double* total, int32_t* count, int K, int64_t* topk_idx, double* topk_val,
+                           hipStream_t s, bool& unsupported);
 
 // phase event helpers (no-ops unless profiling)
 void phase_begin(fia_ctx* c, int phase, hipStream_t s);

@@ -24,12 +24,13 @@
 // Every round takes the best candidate strictly worse than the previous winner under the
 // total order (|v| descending, position ascending, NaN last), so the result does not depend
 // on where the tiles cut a list.
-#include "kern.h"
+// The per-query record and the per-pair pieces (coop_dots, stage_z1, cand_core_ncf) live in
+// cand.h, shared with fia_total_influence (total.hip).
+#include "cand.h"
 
 namespace fia {
 namespace {
 
-constexpr int kCandTile = 256;        // candidates per scoring workgroup, one per thread
 constexpr int kCandRecGrid = 1 << 20; // most workgroups of the per-query kernels (grid-stride)
 
 struct CandArgs {
@@ -51,20 +52,8 @@ struct CandArgs {
 };
 
 template <class M>
-constexpr int cand_rec_size() {
-  // {1 / n_q, c_q}; NCF: + y_user[K], y_item[K], W3g * x_Pg [K], W3g * x_Qg [K]
-  return M::ncf ? 2 + 4 * M::K : 2;
-}
-
-__device__ __forceinline__ double cand_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-template <class M>
 __global__ __launch_bounds__(64) void k_cand_rec(CandArgs A, double* __restrict__ rec) {
-  constexpr int K = M::K, D = M::D, R = cand_rec_size<M>();
+  constexpr int D = M::D, R = cand_rec_size<M>();
   const int lane = threadIdx.x;
   for (int64_t q = blockIdx.x; q < A.Q; q += gridDim.x) {
     const int32_t u = A.qu[q], i = A.qi[q];
@@ -80,44 +69,7 @@ __global__ __launch_bounds__(64) void k_cand_rec(CandArgs A, double* __restrict_
       for (int a = lane; a < R; a += 64) Rq[a] = NAN;
       continue;
     }
-    const double* __restrict__ xq = A.x + q * D;
-    const int64_t n = (A.ptr[0][u + 1] - A.ptr[0][u]) + (A.ptr[1][i + 1] - A.ptr[1][i]);
-    double part = 0.0;
-    if constexpr (!M::ncf) {
-      // M = [1] * 2k + [0, 0]: the biases are not decayed
-      const float* __restrict__ P = A.t[0] + (int64_t)u * K;
-      const float* __restrict__ Qt = A.t[1] + (int64_t)i * K;
-      for (int a = lane; a < K; a += 64) part += xq[a] * (double)P[a] + xq[K + a] * (double)Qt[a];
-    } else {
-      const float* __restrict__ Pm = A.t[0] + (int64_t)u * K;
-      const float* __restrict__ Qm = A.t[1] + (int64_t)i * K;
-      const float* __restrict__ Pg = A.t[2] + (int64_t)u * K;
-      const float* __restrict__ Qg = A.t[3] + (int64_t)i * K;
-      for (int a = lane; a < K; a += 64)
-        part += xq[a] * (double)Pm[a] + xq[K + a] * (double)Qm[a] + xq[2 * K + a] * (double)Pg[a] +
-                xq[3 * K + a] * (double)Qg[a];
-    }
-    part = cand_wave_sum(part);
-    const double inv_n = 1.0 / (double)n;     // n_q = 0: inf, and x is NaN
-    if (lane == 0) {
-      Rq[0] = inv_n;
-      Rq[1] = A.wd * part * inv_n;
-    }
-    if constexpr (M::ncf) {
-      const float* __restrict__ W1 = A.t[4];
-      const float* __restrict__ W3g = A.t[8] + K / 2;
-      for (int c = lane; c < K; c += 64) {
-        double yu = 0.0, yi = 0.0;
-        for (int j = 0; j < K; ++j) {
-          yu = fma((double)W1[(int64_t)j * K + c], xq[j], yu);
-          yi = fma((double)W1[(int64_t)(K + j) * K + c], xq[K + j], yi);
-        }
-        Rq[2 + c] = yu;
-        Rq[2 + K + c] = yi;
-        Rq[2 + 2 * K + c] = (double)W3g[c] * xq[2 * K + c];
-        Rq[2 + 3 * K + c] = (double)W3g[c] * xq[3 * K + c];
-      }
-    }
+    query_record<M>(A, u, i, A.x + q * D, Rq, lane);
   }
 }
 
@@ -128,70 +80,6 @@ __device__ __forceinline__ int64_t cand_query(const int64_t* __restrict__ off, i
     if (off[mid] <= g) lo = mid; else hi = mid - 1;
   }
   return lo;
-}
-
-// Three dot products over a row pair gathered by candidate ids -- r = sum_c [g_c] TA[a][c] TB[b][c],
-// su = sum_c xu[c] TB[b][c] (user side on), si = sum_c xi[c] TA[a][c] (item side on) -- for the 64
-// candidates of a wave, one per lane, with the rows fetched COOPERATIVELY: a lane reading its
-// own two rows touches 64 cache lines per load instruction; here LPC = min(k / 4, 16) lanes
-// share a candidate, each loading 16-B pieces of its rows (a load instruction covers 64 / LPC
-// whole rows), in LPC rounds of 64 / LPC candidates.  The partial sums are added across the LPC
-// lanes by an xor butterfly (the same bits in every lane, the same order wherever the candidate
-// sits) and handed to the candidate's own lane.  The whole wave must call this (shuffles);
-// lanes without a valid candidate load nothing.  xu / xi = xbase + q * XS + XU / XI.
-template <int K, bool WEIGHTED, int XS, int XU, int XI>
-__device__ __forceinline__ void coop_dots(bool valid, int32_t a, int32_t b, int q, bool on_u, bool on_i,
-                                          const float* __restrict__ TA, const float* __restrict__ TB,
-                                          const double* __restrict__ xbase, const float* __restrict__ wgt,
-                                          double& r_out, double& su_out, double& si_out) {
-  constexpr int P = K / 4;                  // 16-B pieces per row
-  constexpr int LPC = P < 16 ? P : 16;      // lanes per candidate
-  constexpr int CPR = 64 / LPC;             // candidates per round
-  constexpr int PPL = P / LPC;              // pieces per lane
-  const int lane = threadIdx.x & 63, sub = lane % LPC, grp = lane / LPC;
-  const int flags = (valid ? 1 : 0) | (on_u ? 2 : 0) | (on_i ? 4 : 0);
-  r_out = su_out = si_out = 0.0;
-#pragma unroll
-  for (int j = 0; j < LPC; ++j) {
-    const int src = j * CPR + grp;          // this round's candidate of the lane's group
-    const int fj = __shfl(flags, src);
-    const int32_t aj = __shfl(a, src), bj = __shfl(b, src);
-    const int qj = __shfl(q, src);
-    double r = 0.0, su = 0.0, si = 0.0;
-    if (fj & 1) {
-      const float4* __restrict__ PA = reinterpret_cast<const float4*>(TA + (int64_t)aj * K);
-      const float4* __restrict__ PB = reinterpret_cast<const float4*>(TB + (int64_t)bj * K);
-      const double* __restrict__ xu = xbase + (int64_t)qj * XS + XU;
-      const double* __restrict__ xi = xbase + (int64_t)qj * XS + XI;
-#pragma unroll
-      for (int t = 0; t < PPL; ++t) {
-        const int pc = sub + t * LPC;
-        const float4 p = PA[pc], w = PB[pc];
-        const double pv[4] = {p.x, p.y, p.z, p.w}, wv[4] = {w.x, w.y, w.z, w.w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int c = 4 * pc + e;
-          if constexpr (WEIGHTED) r = fma((double)wgt[c] * pv[e], wv[e], r);
-          else r = fma(pv[e], wv[e], r);
-          if (fj & 2) su = fma(xu[c], wv[e], su);
-          if (fj & 4) si = fma(xi[c], pv[e], si);
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 1; o < LPC; o <<= 1) {
-      r += __shfl_xor(r, o);
-      su += __shfl_xor(su, o);
-      si += __shfl_xor(si, o);
-    }
-    const int from = (lane % CPR) * LPC;    // the group that had lane's candidate, if this was its round
-    const double gr = __shfl(r, from), gu = __shfl(su, from), gi = __shfl(si, from);
-    if (lane / CPR == j) {
-      r_out = gr;
-      su_out = gu;
-      si_out = gi;
-    }
-  }
 }
 
 // MF: one dot for r-hat, one per matching side with x (d r-hat / d p_u = q_b, d r-hat / d q_i = p_a).
@@ -217,101 +105,19 @@ __device__ __forceinline__ double cand_value_mf(const CandArgs& A, const double*
   return cq + 2.0 * e * (su + si) * inv_n;
 }
 
-// NCF k <= 32: z1 = l1_user[a] + l1_item[b] + b1 of the tile's candidates staged in LDS,
-// unit-major ([c][thread], rows padded by 2), the rows gathered cooperatively as in coop_dots:
-// a row is k / 2 16-B pieces, a wave's load instruction covers 128 / k whole rows.  Above
-// k = 32 the tile's z1 would not fit beside a second workgroup; each lane reads its own rows.
-constexpr int kCandZ1Stride = kCandTile + 2;
-template <int K>
-constexpr bool cand_stage_z1() { return K <= 32; }
-
-template <int K>
-__device__ __forceinline__ void stage_z1(const CandArgs& A, bool valid, int32_t a, int32_t b, double* __restrict__ z1s) {
-  constexpr int PZ = K / 2;                 // 16-B pieces per layer-1 row
-  const int lane = threadIdx.x & 63, wbase = threadIdx.x & ~63;
-#pragma unroll
-  for (int it = 0; it < PZ; ++it) {
-    const int e = it * 64 + lane, row = e / PZ, pc = e % PZ;
-    const int vr = __shfl((int)valid, row);
-    const int32_t ar = __shfl(a, row), br = __shfl(b, row);
-    if (vr) {
-      const double2 lu = reinterpret_cast<const double2*>(A.l1[0] + (int64_t)ar * K)[pc];
-      const double2 li = reinterpret_cast<const double2*>(A.l1[1] + (int64_t)br * K)[pc];
-      z1s[(2 * pc) * kCandZ1Stride + wbase + row] = lu.x + li.x + (double)A.t[5][2 * pc];
-      z1s[(2 * pc + 1) * kCandZ1Stride + wbase + row] = lu.y + li.y + (double)A.t[5][2 * pc + 1];
-    }
-  }
-}
-
-// NCF: z1 from the per-entity layer-1 rows; the MLP's share of x . g_c is y_side . d1 with
-// d1 = 1[z1 > 0] (W2 (1[z2 > 0] W3m)) -- W1 is never touched per candidate.
-// W2 / b2 / W3 come from LDS (fp64) up to k = 64 and from wave-uniform global loads above.
+// NCF: the MLP's share of r-hat and of x . g_c from cand_core_ncf with the query's y_side
+// vectors; GMF (coop_dots, by the caller): rg = W3g . (Pg_a * Qg_b),
+// sg = x_Pg . (W3g * Qg_b) + x_Qg . (W3g * Pg_a)
 template <int K>
 __device__ __forceinline__ double cand_value_ncf(const CandArgs& A, const double* __restrict__ rec,
                                                  const NCFWeights<(K <= 64 ? K : 2)>& w, int64_t q, int32_t a,
                                                  int32_t b, float y, bool on_u, bool on_i, double rg, double sg,
                                                  const double* __restrict__ z1col) {
-  constexpr int H = K / 2, R = 2 + 4 * K;
-  constexpr bool lds = K <= 64;
+  constexpr int R = 2 + 4 * K;
   const double* __restrict__ Rq = rec + q * R;
   const double inv_n = Rq[0], cq = Rq[1];
-  const double* __restrict__ l1u = A.l1[0] + (int64_t)a * K;
-  const double* __restrict__ l1i = A.l1[1] + (int64_t)b * K;
-  const float* __restrict__ b1 = A.t[5];
-  const float* __restrict__ gW2 = A.t[6];
-  const float* __restrict__ gb2 = A.t[7];
-  const float* __restrict__ gW3 = A.t[8];
-  auto W2 = [&](int c, int h) -> double {
-    if constexpr (lds) return w.W2[c * H + h]; else return (double)gW2[c * H + h];
-  };
-  auto W3 = [&](int j) -> double {
-    if constexpr (lds) return w.W3[j]; else return (double)gW3[j];
-  };
-  // One pass over the k first-layer units per block of HC second-layer units, with two
-  // accumulators per unit h: z2[h] = b2[h] + sum_c W2[c][h] relu(z1[c]) and
-  // wy[h] = sum_c W2[c][h] 1[z1[c] > 0] y[c] (y = the matching sides' y_side), because
-  //   y . d1 = sum_c y[c] 1[z1[c] > 0] sum_h W2[c][h] d2[h] = sum_h d2[h] wy[h],  d2[h] = 1[z2[h] > 0] W3m[h]
-  // -- no d1 / d2 vector is kept, and the registers are 2 HC doubles at every k.
-  constexpr int HC = H < 16 ? H : 16;
-  const double* __restrict__ yu = Rq + 2;
-  const double* __restrict__ yi = Rq + 2 + K;
-  const bool on_any = on_u || on_i;
-  double r = 0.0, s = 0.0;
-#pragma unroll 1
-  for (int h0 = 0; h0 < H; h0 += HC) {
-    double z2[HC], wy[HC];
-#pragma unroll
-    for (int h = 0; h < HC; ++h) {
-      if constexpr (lds) z2[h] = w.b2[h0 + h]; else z2[h] = (double)gb2[h0 + h];
-      wy[h] = 0.0;
-    }
-#pragma unroll 1
-    for (int c = 0; c < K; ++c) {
-      double z1;
-      if constexpr (cand_stage_z1<K>()) z1 = z1col[c * kCandZ1Stride];
-      else z1 = l1u[c] + l1i[c] + (double)b1[c];
-      const bool pos1 = z1 > 0.0;
-      const double h1 = pos1 ? z1 : 0.0;
-      double yv = 0.0;
-      if (pos1 && on_u) yv += yu[c];
-      if (pos1 && on_i) yv += yi[c];
-#pragma unroll
-      for (int h = 0; h < HC; ++h) {
-        const double w2 = W2(c, h0 + h);
-        z2[h] = fma(w2, h1, z2[h]);
-        if (on_any) wy[h] = fma(w2, yv, wy[h]);
-      }
-    }
-#pragma unroll
-    for (int h = 0; h < HC; ++h) {
-      const double w3 = W3(h0 + h);
-      if (z2[h] > 0.0) {
-        r = fma(w3, z2[h], r);
-        s = fma(w3, wy[h], s);
-      }
-    }
-  }
-  // GMF (coop_dots, by the caller): rg = W3g . (Pg_a * Qg_b), sg = x_Pg . (W3g * Qg_b) + x_Qg . (W3g * Pg_a)
+  double r, s;
+  cand_core_ncf<K>(A, w, a, b, on_u, on_i, Rq + 2, Rq + 2 + K, z1col, r, s);
   s += sg;
   r += rg + (double)A.t[9][0];
   const double e = r - (double)y;

@@ -39,6 +39,7 @@ SIGNATURES = {
     "fia_query_batch": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
     "fia_query_batch_x": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
     "fia_score_candidates": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
+    "fia_total_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "fia_num_params": (ctypes.c_int, [_P]),
     "fia_set_profiling": (ctypes.c_int, [_P, ctypes.c_int]),
     "fia_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I64)]),
@@ -130,6 +131,7 @@ class Context(object):
         rc = self.lib.fia_build_index(self.h, users.numel(), U, I, _ptr(users), _ptr(items), _ptr(ratings),
                                       _stream())
         self._check(rc, "fia_build_index")
+        self.n_train = users.numel()
 
     def prepare(self):
         self.full_prepared = False
@@ -234,6 +236,44 @@ class Context(object):
                                            int(total), _ptr(cand_user), _ptr(cand_item), _ptr(cand_rating),
                                            _ptr(influence), int(K), _ptr(topk_pos), _ptr(topk_val), _stream())
         self._check(rc, "fia_score_candidates")
+
+    def total_influence(self, qu, qi, x, total=None, count=None, K=0, topk_idx=None, topk_val=None):
+        """fia_total_influence: for every train row the sum of its influence on the queries
+        (qu, qi) with inverse HVPs x (float64 cuda tensor [Q * D], reference theta order) --
+        the scatter-add of query_batch_x's influence by rel_idx -- into total (float64
+        [n_train]) and count (int32 [n_train]); with K the K rows of largest |total| (topk_idx
+        int64 [K], topk_val float64 [K]).  n_train is the size of the built index: total and
+        count, when given, must hold that many values."""
+        import torch
+        self._need_int32(qu, "qu")
+        self._need_int32(qi, "qi")
+        self._need_int32(count, "count")
+        if qi.numel() != qu.numel():
+            raise ValueError("qu and qi must have the same length")
+        if x.dtype != torch.float64 or not x.is_contiguous() or not x.is_cuda:
+            raise TypeError("x must be a contiguous torch.float64 device (cuda) tensor")
+        if x.numel() < qu.numel() * self.num_params():
+            raise ValueError("x holds %d values, %d queries need %d" % (
+                x.numel(), qu.numel(), qu.numel() * self.num_params()))
+        if total is not None and total.dtype != torch.float64:
+            raise TypeError("total must be a torch.float64 tensor")
+        if topk_idx is not None and topk_idx.dtype != torch.int64:
+            raise TypeError("topk_idx must be a torch.int64 tensor")
+        if topk_val is not None and topk_val.dtype != torch.float64:
+            raise TypeError("topk_val must be a torch.float64 tensor")
+        for t, name in ((qu, "qu"), (qi, "qi"), (total, "total"), (count, "count"), (topk_idx, "topk_idx"),
+                        (topk_val, "topk_val")):
+            if t is not None and not (t.is_cuda and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous device (cuda) tensor" % name)
+        n_train = getattr(self, "n_train", None)
+        for t, name in ((total, "total"), (count, "count")):
+            if t is not None and n_train is not None and t.numel() < n_train:
+                raise ValueError("%s holds %d values, the index has %d train rows" % (name, t.numel(), n_train))
+        if K and (topk_idx is None or topk_val is None or min(topk_idx.numel(), topk_val.numel()) < K):
+            raise ValueError("top-K outputs must hold K values")
+        rc = self.lib.fia_total_influence(self.h, qu.numel(), _ptr(qu), _ptr(qi), _ptr(x), _ptr(total), _ptr(count),
+                                          int(K), _ptr(topk_idx), _ptr(topk_val), _stream())
+        self._check(rc, "fia_total_influence")
 
     # ---- profiling ----
     def set_profiling(self, on, phases=None):

@@ -460,6 +460,114 @@ class GenericNeuralNet(object):
             out["topk_val"] = tv[:Q * K].cpu().numpy().reshape(Q, K)
         return out
 
+    def _host_num_params(self):
+        """D of theta_t from the model's shape alone (no GPU context needed)."""
+        k = int(self.embedding_size)
+        return 2 * k + 2 if self.MODEL_ID == _lib.FIA_MODEL_MF else 4 * k
+
+    def get_total_influence(self, test_indices, weights=None, K=0, full=True, inverse_hvp=None):
+        """Influence of EVERY training rating on a set of predictions (one fia_total_influence
+        call; the reference asserts len(test_indices) == 1, matrix_factorization.py:179):
+
+            total[j] = sum_q weights[q] * (influence of train row j on test rating test_indices[q])
+
+        summed over both occurrences when row j is the test pair itself -- the scatter-add by
+        rel_idx of get_influence_batch's influence, computed from per-user / per-item sums of the
+        queries without walking the related lists (include/fia.h).  count[j] is how often row j
+        occurs in the related lists of the batch.  x_q comes from one fia_query_batch call (no
+        per-rating vectors), or from inverse_hvp (float64 [Q, D], reference theta order); with
+        weights (float [Q], finite) x_q is scaled by weights[q] on the device.  A test rating
+        with an empty related set contributes nothing.  weights, K and the inverse_hvp size are
+        checked on the host (ValueError) before any GPU call.  Returns dict(x [Q, D] unscaled,
+        total float64 [n_train] and count int32 [n_train] with full, topk_idx int64 [K] and
+        topk_val float64 [K] with K: the train rows of largest |total| among the touched rows,
+        ties to the lower row, -1 / NaN where fewer than K rows are touched)."""
+        Q = len(test_indices)
+        D = self._host_num_params()
+        w = None
+        if weights is not None:
+            w = np.asarray(weights, np.float64)
+            if w.ndim != 1 or w.size != Q:
+                raise ValueError("weights must hold len(test_indices) = %d values" % Q)
+            if not np.isfinite(w).all():
+                raise ValueError("weights must be finite")
+        if int(K) != K or not 0 <= int(K) <= _lib.FIA_MAX_TOPK:
+            raise ValueError("K must be in [0, %d]" % _lib.FIA_MAX_TOPK)
+        K = int(K)
+        xin = None
+        if inverse_hvp is not None:
+            xin = np.ascontiguousarray(np.asarray(inverse_hvp, np.float64).reshape(-1))
+            if xin.size != Q * D:
+                raise ValueError("inverse_hvp must hold %d x %d values" % (Q, D))
+        if not full and K == 0:
+            raise ValueError("nothing to return: full=False needs K > 0")
+        import torch
+        qu, qi = self._query_tensors(test_indices)
+        dev = self.ctx.torch_device
+        if xin is not None:
+            x = torch.from_numpy(xin).to(dev) if Q else torch.empty(1, dtype=torch.float64, device=dev)
+        else:
+            # (the count also rejects query ids out of range and queries outside a prepare_for cover)
+            offsets, total_rel = self.ctx.count_related(qu, qi)
+            x = torch.empty(max(Q * D, 1), dtype=torch.float64, device=dev)
+            self.ctx.query_batch(qu, qi, offsets, total_rel, None, None, x, 0, None, None, None)
+        xs = x
+        if w is not None and Q:
+            xs = (x[:Q * D].view(Q, D) * torch.from_numpy(w).to(dev)[:, None]).reshape(-1).contiguous()
+        n = self.ctx.n_train
+        total = torch.empty(max(n, 1), dtype=torch.float64, device=dev) if full else None
+        count = torch.empty(max(n, 1), dtype=torch.int32, device=dev) if full else None
+        ti = torch.empty(max(K, 1), dtype=torch.int64, device=dev) if K else None
+        tv = torch.empty(max(K, 1), dtype=torch.float64, device=dev) if K else None
+        self.ctx.total_influence(qu, qi, xs, total, count, K, ti, tv)
+        out = dict(x=x[:Q * D].cpu().numpy().reshape(Q, D))
+        if full:
+            out["total"] = total[:n].cpu().numpy()
+            out["count"] = count[:n].cpu().numpy()
+        if K:
+            out["topk_idx"] = ti[:K].cpu().numpy()
+            out["topk_val"] = tv[:K].cpu().numpy()
+        return out
+
+    def _predict_device(self, qu, qi):
+        """r-hat(u, i) in fp64 on the device from the uploaded (float32) parameter tables."""
+        import torch
+        k = int(self.embedding_size)
+        u, i = qu.long(), qi.long()
+        t = [p.double() for p in self._dev_params]
+        if self.MODEL_ID == _lib.FIA_MODEL_MF:
+            return (t[0].view(-1, k)[u] * t[1].view(-1, k)[i]).sum(1) + t[2][u] + t[3][i] + t[4][0]
+        h = k // 2
+        x0 = torch.cat([t[0].view(-1, k)[u], t[1].view(-1, k)[i]], 1)
+        h1 = torch.relu(x0 @ t[4].view(2 * k, k) + t[5])
+        h2 = torch.relu(h1 @ t[6].view(k, h) + t[7])
+        gmf = t[2].view(-1, k)[u] * t[3].view(-1, k)[i]
+        return h2 @ t[8][:h] + gmf @ t[8][h:] + t[9][0]
+
+    def get_influence_on_test_set_loss(self, test_indices, K=0):
+        """The Koh-Liang aggregate over a test set: the influence of every training rating on the
+        mean squared test error L = (1 / Q) sum_q (r-hat(u_q, i_q) - y_q)^2, to first order
+
+            total[j] = sum_q 2 (r-hat(u_q, i_q) - y_q) / Q * (influence of row j on r-hat(u_q, i_q))
+
+        = get_total_influence(test_indices, weights) with weights[q] = 2 (r-hat_q - y_q) / Q,
+        y_q from data_sets["test"].labels and r-hat_q computed in fp64 on the device from the
+        uploaded tables.  Sign: the per-query influence is the predicted change of r-hat(test)
+        when the training rating is REMOVED (experiments.test_retraining compares it with r-hat
+        after leave-one-out retraining minus r-hat before), so total[j] > 0 means that removing
+        rating j raises the mean test loss -- the rating helps -- and total[j] < 0 that removing
+        it lowers the loss.  Returns get_total_influence's dict plus weights [Q]."""
+        Q = len(test_indices)
+        qu, qi = self._query_tensors(test_indices)
+        y = np.asarray(self.data_sets["test"].labels, np.float64).reshape(-1)[np.asarray(test_indices, np.int64)]
+        if Q:
+            w = (2.0 * (self._predict_device(qu, qi).cpu().numpy() - y) / Q)
+        else:
+            w = np.zeros(0)
+        out = self.get_total_influence(test_indices, weights=w, K=K, full=True)
+        out["weights"] = w
+        return out
+
     def _score_one_query_candidates(self, test_index, x, X, Y):
         off = np.array([0, len(Y)], np.int64)
         return self.get_candidate_influence_batch([test_index], off, X, Y, K=0, full=True,

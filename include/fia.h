@@ -23,6 +23,9 @@
  *   phantom-point branch of get_influence_on_test_loss   fia_score_candidates
  *     (train_idx None, X / Y given: mf:228-235, and the
  *      same branch of NCF.py)
+ *   (none: get_influence_on_test_loss asserts            fia_total_influence
+ *     len(test_indices) == 1, mf:179 -- the influence of
+ *     every train row on a SET of predictions)
  *
  * Conventions
  *   - All array arguments are DEVICE pointers owned by the caller (PyTorch).
@@ -218,6 +221,49 @@ int fia_score_candidates(fia_ctx* ctx, int64_t num_queries, const int32_t* q_use
                          double* influence,               /* device [total_cand], nullable                */
                          int K, int64_t* topk_pos, double* topk_val,   /* [Q*K], K in [0, FIA_MAX_TOPK]   */
                          void* stream);
+
+/* Total influence of every TRAIN row on a batch of predictions.  The reference has no
+ * counterpart: get_influence_on_test_loss asserts len(test_indices) == 1
+ * (matrix_factorization.py:179).  For train row j = (a, b, y) and queries q = (u_q, i_q) with
+ * inverse HVPs x_q = x[q*D .. ) (reference theta order, as fia_score_candidates):
+ *   total[j] = sum_q m_q(j) * I_q(j)
+ *   I_q(j)   = x_q . (2 e_j g_j + wd * M * theta_t(q)) / n_q    the value fia_query_batch_x writes
+ *                                                               for row j in q's related list
+ *   m_q(j)   = [a == u_q] + [b == i_q]                          how often j occurs in that list
+ *                                                               (2: q's pair is row j's own pair)
+ *   count[j] = sum_q m_q(j)
+ * i.e. total is the scatter-add of fia_query_batch_x's influence by rel_idx, and count the
+ * histogram of rel_idx -- computed without the related lists: I_q(j) is linear in x_q and the
+ * gradient block that multiplies it depends on the train row only, so each user's and each
+ * item's queries are summed first and every train row is scored once (O(Q D + N D)).
+ *   - A row no query touches (count 0) gets exactly +0.0.
+ *   - A query with n_q = 0 contributes nothing (its NaN x reaches no row); a query whose id is
+ *     outside [0, num_users) x [0, num_items) contributes nothing and is never used as an index.
+ *   - A non-finite x_q reaches only the rows that query touches.
+ *   - x may be any vector: scaling x_q by w_q gives the weighted sum sum_q w_q m_q(j) I_q(j).
+ * topk (K in [0, FIA_MAX_TOPK]; 0 = off): the K train rows of largest |total| among the rows
+ * with count > 0, in fia_query_batch's order with the train row as position (|v| descending,
+ * ties: lower train row first, NaN last), as train row (topk_idx) and signed total (topk_val),
+ * device arrays [K]; unused slots hold -1 / NaN.  total and count may be NULL; with K == 0 too
+ * the call is FIA_ERR_INVALID.
+ * Needs params, index and a prepare (else FIA_ERR_STATE).  It reads only the parameter tables,
+ * the index, the train-pair table and, NCF, the dense layer-1 rows, which every prepare writes
+ * for all entities: after fia_prepare_for the results are bitwise those after fia_prepare,
+ * whatever the cover.  Ordered on `stream`, no host synchronisation; of a pending small-k Gram
+ * pass it waits only for the NCF layer-1 rows.  The same inputs give the same bits on every call:
+ * no floating-point atomics, each entity's queries are summed in ascending query position.
+ * Batch limit: num_queries <= FIA_TOTAL_MAX_QUERIES (2^30, so that count fits in 32 bits): a
+ * larger batch is refused with FIA_ERR_INVALID before anything is reserved or launched -- split
+ * it, totals add.  num_queries == 0 zeroes total and count, fills the top-K slots with -1 / NaN
+ * and returns FIA_OK.  Every size fia_score_candidates is built for (MF and NCF,
+ * k in {8, 16, 32, 64, 128, 256}); anything else is FIA_ERR_UNSUPPORTED. */
+#define FIA_TOTAL_MAX_QUERIES (1LL << 30)
+int fia_total_influence(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item,
+                        const double* x,          /* device [Q*D], reference theta order, as fia_score_candidates */
+                        double* total,            /* device [n_train], nullable                                  */
+                        int32_t* count,           /* device [n_train], nullable                                  */
+                        int K, int64_t* topk_idx, double* topk_val,   /* device [K], K in [0, FIA_MAX_TOPK]      */
+                        void* stream);
 
 /* Number of restricted parameters D of the registered model (0 if none). */
 int fia_num_params(const fia_ctx* ctx);
