@@ -241,7 +241,7 @@ int fia_destroy(fia_ctx* c) {
                            &c->gcnt,   &c->gstart, &c->grank,    &c->gq,        &c->qbase,    &c->gscan,
                            &c->wstart, &c->witems, &c->resid,  &c->qwork,  &c->xb,       &c->syslist,
                            &c->cpllist, &c->lscr, &c->mark, &c->d1tab, &c->slices, &c->wfrag,
-                           &c->tkeys, &c->tvals, &c->tagg, &c->tslot, &c->tword, &c->tsort};
+                           &c->tkeys, &c->tvals, &c->tagg, &c->tslot, &c->tword, &c->tsort, &c->rowrec, &c->gxq};
     for (auto* b : bufs) rel(*b);
     if (can_free) (void)hipStreamSynchronize(ds);   // the stream-ordered frees complete
     if (c->aux && !capturing) (void)hipStreamDestroy(c->aux);
@@ -556,6 +556,40 @@ int fia_total_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t*
     hipError_t e = fia::total_influence(c, Q, qu, qi, x, total, count, K, topk_idx, topk_val, s, unsup);
     if (unsup) return fail(c, FIA_ERR_UNSUPPORTED, "model/k not supported");
     if (e != hipSuccess) return hip_fail(c, e, "fia_total_influence");
+    return FIA_OK;
+  })
+}
+
+int fia_group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* grp_offsets,
+                        int64_t num_groups, const int64_t* mem_offsets, int64_t total_members, const int32_t* mem_row,
+                        double* group, double* first_order, double* dtheta, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    // the batch bounds come first: nothing of an oversized batch is looked at
+    if (Q < 0 || Q >= (1LL << 31)) return fail(c, FIA_ERR_INVALID, "num_queries out of range");
+    if (num_groups < 0 || num_groups > FIA_GROUP_MAX_GROUPS)
+      return fail(c, FIA_ERR_INVALID, "num_groups out of range [0, 2^31 - 1]: split the batch");
+    if (total_members < 0 || total_members > FIA_GROUP_MAX_MEMBERS)
+      return fail(c, FIA_ERR_INVALID, "total_members out of range [0, 2^31 - 1]: split the batch");
+    if (!c->p.valid || !c->idx.valid) return fail(c, FIA_ERR_STATE, "params/index missing");
+    if (!c->prepared) return fail(c, FIA_ERR_STATE, "fia_prepare has not been called since params/index changed");
+    if (!group && !first_order && !dtheta)
+      return fail(c, FIA_ERR_INVALID, "no output requested (group, first_order, dtheta)");
+    if (Q == 0 || num_groups == 0) return FIA_OK;
+    if (!qu || !qi || !grp_offsets || !mem_offsets) return fail(c, FIA_ERR_INVALID, "null query or offset array");
+    if (total_members > 0 && !mem_row) return fail(c, FIA_ERR_INVALID, "null member array");
+    if (!fia::group_supported(c->p.model, c->p.k))
+      return fail(c, FIA_ERR_UNSUPPORTED,
+                  "fia_group_influence is built for MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32} (the full "
+                  "packed system in LDS); the large-k models keep their systems in device memory");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_group_influence"); rc != FIA_OK) return rc;
+    // the Gram caches of a pending small-k pass are read: join it, as fia_query_batch's solve does
+    if (hipError_t es = fia::join_prepare(c, s); es != hipSuccess) return hip_fail(c, es, "fia_group_influence");
+    hipError_t e = fia::group_influence(c, Q, qu, qi, grp_offsets, num_groups, mem_offsets, total_members, mem_row,
+                                        group, first_order, dtheta, s);
+    if (e != hipSuccess) return hip_fail(c, e, "fia_group_influence");
     return FIA_OK;
   })
 }

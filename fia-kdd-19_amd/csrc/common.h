@@ -233,6 +233,10 @@ struct fia_ctx {
   // fia_total_influence (total.hip), per batch: sort keys / queries (in, out) of the 2Q (entity,
   // query) pairs, per-group aggregates, entity -> group, per-query / per-group words, sort scratch
   fia::DevBuf tkeys, tvals, tagg, tslot, tword, tsort;
+  // fia_group_influence (group.hip): train row -> {user, item, rating, list position} (per index),
+  // and per batch the queries' x_q = H^-1 v [Q * D] for first_order
+  fia::DevBuf rowrec, gxq;
+  uint64_t rowrec_version = ~0ull;
   // large-k path (bigk.hip): per-list-position entity, per-train-row residual / NCF backward
   // vectors, per-query Hessian inputs and solutions, solve lists and LDL^T scratch
   fia::DevBuf self[2];    // int32 [N] entity owning list position p of side s
@@ -391,6 +395,14 @@ hipError_t score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int3
 hipError_t total_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const double* x,
                            double* total, int32_t* count, int K, int64_t* topk_idx, double* topk_val,
                            hipStream_t s, bool& unsupported);
+
+// fia_group_influence (group.hip): per group of train rows the re-solved system with the
+// group's rows removed; small k only (group_supported); scratch: c->rowrec, c->gxq
+bool group_supported(int model, int k);
+hipError_t group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* grp_offsets,
+                           int64_t num_groups, const int64_t* mem_offsets, int64_t total_members,
+                           const int32_t* mem_row, double* group, double* first_order, double* dtheta,
+                           hipStream_t s);
 
 // phase event helpers (no-ops unless profiling)
 void phase_begin(fia_ctx* c, int phase, hipStream_t s);

@@ -1,0 +1,176 @@
+// Device code of the full-D per-query system, shared by models.hip (k_solve, k_record_x and
+// the side-system solves' prologue) and group.hip (fia_group_influence): the LDS LDL^T, the
+// query prologue (theta_t, v = d r-hat / d theta_t, r-hat of one pair) and the assembly of the
+// packed coupled Hessian from the two entity Gram caches.  One wave (kSolveThreads) per system
+// unless a function says otherwise.
+#pragma once
+
+#include "kern.h"
+
+namespace fia {
+
+// In-place LDL^T of the packed lower block [lo, hi) followed by L D L^T x = v.
+template <int D>
+__device__ void ldlt_solve(double* H, double* v, double* d, double* w, int lo, int hi) {
+  const int lane = threadIdx.x;
+  for (int j = lo; j < hi; ++j) {
+    for (int c = lo + lane; c < j; c += kSolveThreads) w[c] = H[tri(j, c)] * d[c];
+    __syncthreads();
+    for (int r = j + lane; r < hi; r += kSolveThreads) {
+      const double* Lr = H + tri(r, 0);
+      double t = Lr[j];
+      for (int c = lo; c < j; ++c) t = fma(-Lr[c], w[c], t);
+      if (r == j) d[j] = t; else H[tri(r, j)] = t;
+    }
+    __syncthreads();
+    const double dj = d[j];
+    for (int r = j + 1 + lane; r < hi; r += kSolveThreads) H[tri(r, j)] /= dj;
+    __syncthreads();
+  }
+  for (int j = lo; j < hi; ++j) {
+    const double yj = v[j];
+    for (int r = j + 1 + lane; r < hi; r += kSolveThreads) v[r] = fma(-H[tri(r, j)], yj, v[r]);
+    __syncthreads();
+  }
+  for (int j = lo + lane; j < hi; j += kSolveThreads) v[j] /= d[j];
+  __syncthreads();
+  for (int j = hi - 1; j >= lo; --j) {
+    const double xj = v[j];
+    const double* Lj = H + tri(j, 0);
+    for (int c = lo + lane; c < j; c += kSolveThreads) v[c] = fma(-Lj[c], xj, v[c]);
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+  return x;
+}
+
+
+// theta_t, v = d r(u,i)/d theta_t (gnn:155, mf:194,201 / ncf:222,229) and r-hat(u,i) of one
+// query into the workgroup's LDS arrays th[D] / g[D] (NTH threads cooperate; r-hat is
+// valid in the first wave)
+template <class M, int NTH>
+__device__ double solve_prologue(const QueryArgs& A, int32_t u, int32_t i, double* __restrict__ th,
+                                 double* __restrict__ g, double* __restrict__ sh, const NCFWeights<M::ncf ? M::K : 2>& w,
+                                 const double* __restrict__ sW1, const double* __restrict__ sb1) {
+  constexpr int K = M::K, Ds = M::Ds;
+  const int lane = threadIdx.x;
+  double rhat_ui = 0.0;
+  if constexpr (!M::ncf) {
+    const float* P = A.t[0];
+    const float* Qt = A.t[1];
+    for (int a = lane; a < K; a += NTH) {
+      th[a] = P[(int64_t)u * K + a];
+      th[Ds + a] = Qt[(int64_t)i * K + a];
+      g[a] = Qt[(int64_t)i * K + a];           // user block of v: q_i
+      g[Ds + a] = P[(int64_t)u * K + a];       // item block of v: p_u
+    }
+    if (lane == 0) {
+      th[K] = A.t[2][u];
+      th[Ds + K] = A.t[3][i];
+      g[K] = 1.0;
+      g[Ds + K] = 1.0;
+    }
+    __syncthreads();
+    double part = 0.0;
+    for (int a = lane; a < K; a += NTH) part += th[a] * th[Ds + a];
+    rhat_ui = wave_sum(part) + th[K] + th[Ds + K] + (double)A.t[4][0];
+  } else {
+    constexpr int H2 = K / 2;
+    const float* Pm = A.t[0];
+    const float* Qm = A.t[1];
+    const float* Pg = A.t[2];
+    const float* Qg = A.t[3];
+    double* z1 = sh;            // K
+    double* d2 = sh + K;        // K/2
+    double* d1 = sh + 2 * K;    // K
+    for (int a = lane; a < K; a += NTH) {
+      th[a] = Pm[(int64_t)u * K + a];
+      th[K + a] = Pg[(int64_t)u * K + a];
+      th[Ds + a] = Qm[(int64_t)i * K + a];
+      th[Ds + K + a] = Qg[(int64_t)i * K + a];
+      z1[a] = A.l1[0][(int64_t)u * K + a] + A.l1[1][(int64_t)i * K + a] + sb1[a];
+    }
+    __syncthreads();
+    double mlp_part = 0.0;
+    for (int dd2 = lane; dd2 < H2; dd2 += NTH) {
+      double z2 = w.b2[dd2];
+      for (int c = 0; c < K; ++c) z2 = fma(w.W2[c * H2 + dd2], z1[c] > 0.0 ? z1[c] : 0.0, z2);
+      const bool on = z2 > 0.0;
+      d2[dd2] = on ? w.W3[dd2] : 0.0;
+      mlp_part += on ? w.W3[dd2] * z2 : 0.0;
+    }
+    double gmf_part = 0.0;
+    for (int a = lane; a < K; a += NTH) gmf_part += w.W3[H2 + a] * th[K + a] * th[Ds + K + a];
+    rhat_ui = wave_sum(mlp_part + gmf_part) + (double)A.t[9][0];
+    __syncthreads();
+    for (int c = lane; c < K; c += NTH) {
+      double t = 0.0;
+      for (int dd2 = 0; dd2 < H2; ++dd2) t = fma(w.W2[c * H2 + dd2], d2[dd2], t);
+      d1[c] = z1[c] > 0.0 ? t : 0.0;
+    }
+    __syncthreads();
+    for (int a = lane; a < 2 * K; a += NTH) {
+      // rows a < K: W1[:k] (Pm part, user block); rows a >= K: W1[k:] (Qm part, item block)
+      double s = 0.0;
+      for (int c = 0; c < K; ++c) s = fma(sW1[a * K + c], d1[c], s);
+      if (a < K) g[a] = s; else g[Ds + (a - K)] = s;
+    }
+    for (int a = lane; a < K; a += NTH) {
+      g[K + a] = w.W3[H2 + a] * th[Ds + K + a];        // d r/d Pg_u = W3g * Qg_i
+      g[Ds + K + a] = w.W3[H2 + a] * th[K + a];        // d r/d Qg_i = W3g * Pg_u
+    }
+  }
+  __syncthreads();
+  return rhat_ui;
+}
+
+// The packed lower triangle of the full D x D Hessian of query (u, i) (n related ratings,
+// v in g[D], r-hat(u, i) given) from the two entity Gram caches:
+//   H = (2/n) (A_u (+) B_i) + the (u, i) train rows' second copies and coupling + wd M + damping I
+// One wave; the caller synchronises before reading H.  Returns whether (u, i) is a train
+// row (then the user and item blocks are coupled).
+template <class M>
+__device__ __forceinline__ bool assemble_hessian(const QueryArgs& A, int32_t u, int32_t i, int64_t n, double rhat_ui,
+                                                 const double* __restrict__ g, double* __restrict__ H) {
+  constexpr int K = M::K, Ds = M::Ds, D = M::D, GS = Ds * (Ds + 1) / 2;
+  const int lane = threadIdx.x;
+  const double s2n = 2.0 / (double)n;
+  // ---- the (u,i) pair among the train rows (pair set built with the index) ----
+  double cdup, rsum;
+  A.pairs.lookup((unsigned long long)u * (unsigned long long)A.I + (unsigned long long)i, cdup, rsum);
+  const bool coupled = cdup > 0.0;
+  const double esum = cdup * rhat_ui - rsum;
+  const double* Gu = A.gram[0] + (int64_t)u * ((GS + 1) & ~1);
+  const double* Gi = A.gram[1] + (int64_t)i * ((GS + 1) & ~1);
+  for (int t = lane; t < D * (D + 1) / 2; t += kSolveThreads) {
+    int r = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
+    while (tri(r + 1, 0) <= t) ++r;
+    while (tri(r, 0) > t) --r;
+    const int c = t - tri(r, 0);
+    double h = 0.0;
+    if (r < Ds) {
+      h = s2n * (Gu[gidx<M>(r, c)] + cdup * g[r] * g[c]);
+    } else if (c >= Ds) {
+      const int rr = r - Ds, cc = c - Ds;
+      h = s2n * (Gi[gidx<M>(rr, cc)] + cdup * g[r] * g[c]);
+    } else if (coupled) {
+      // cross block: item row rr, user col c: 2 (c g_i g_u^T + esum * d2r/dtheta_i dtheta_u)
+      const int rr = r - Ds;
+      h = s2n * 2.0 * cdup * g[r] * g[c];
+      if constexpr (!M::ncf) {
+        if (rr == c && c < K) h += s2n * 2.0 * esum;                     // d2 r / dp_u dq_i = I
+      } else {
+        if (rr == c && c >= K) h += s2n * 2.0 * esum * (double)A.t[8][K / 2 + (c - K)];   // diag(W3g)
+      }
+    }
+    if (r == c) h += (M::decayed(r < Ds ? r : r - Ds) ? A.wd : 0.0) + A.damping;
+    H[t] = h;
+  }
+  return coupled;
+}
+
+}  // namespace fia

@@ -40,6 +40,7 @@ SIGNATURES = {
     "fia_query_batch_x": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
     "fia_score_candidates": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "fia_total_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
+    "fia_group_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
     "fia_num_params": (ctypes.c_int, [_P]),
     "fia_set_profiling": (ctypes.c_int, [_P, ctypes.c_int]),
     "fia_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I64)]),
@@ -274,6 +275,46 @@ class Context(object):
         rc = self.lib.fia_total_influence(self.h, qu.numel(), _ptr(qu), _ptr(qi), _ptr(x), _ptr(total), _ptr(count),
                                           int(K), _ptr(topk_idx), _ptr(topk_val), _stream())
         self._check(rc, "fia_total_influence")
+
+    def group_influence(self, qu, qi, grp_offsets, mem_offsets, mem_row, group=None, first_order=None,
+                        dtheta=None):
+        """fia_group_influence: for every group of train rows (group g of query q for g in
+        grp_offsets[q]:grp_offsets[q+1], its members mem_row[mem_offsets[g]:mem_offsets[g+1]])
+        the predicted change of r-hat when the rows are removed together -- the system with the
+        rows' terms taken out, solved again -- into group (float64 [G]), the sum of the rows'
+        single-rating influences into first_order (float64 [G]) and the parameter step into
+        dtheta (float64 [G * D], reference theta order).  Offsets are int64, rows int32."""
+        import torch
+        for t, name in ((qu, "qu"), (qi, "qi"), (mem_row, "mem_row")):
+            self._need_int32(t, name)
+        if qi.numel() != qu.numel():
+            raise ValueError("qu and qi must have the same length")
+        Q = qu.numel()
+        if grp_offsets.dtype != torch.int64 or grp_offsets.numel() != Q + 1:
+            raise TypeError("grp_offsets must be a torch.int64 tensor of Q + 1 values")
+        if mem_offsets.dtype != torch.int64 or mem_offsets.numel() < 1:
+            raise TypeError("mem_offsets must be a torch.int64 tensor of G + 1 values")
+        G = mem_offsets.numel() - 1
+        for t, name in ((group, "group"), (first_order, "first_order"), (dtheta, "dtheta")):
+            if t is not None and t.dtype != torch.float64:
+                raise TypeError("%s must be a torch.float64 tensor" % name)
+        for t, name in ((qu, "qu"), (qi, "qi"), (grp_offsets, "grp_offsets"), (mem_offsets, "mem_offsets"),
+                        (mem_row, "mem_row"), (group, "group"), (first_order, "first_order"), (dtheta, "dtheta")):
+            if t is not None and not (t.is_cuda and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous device (cuda) tensor" % name)
+        if group is None and first_order is None and dtheta is None:
+            raise ValueError("no output requested (group, first_order, dtheta)")
+        for t, name in ((group, "group"), (first_order, "first_order")):
+            if t is not None and t.numel() < G:
+                raise ValueError("%s holds %d values, the batch has %d groups" % (name, t.numel(), G))
+        if dtheta is not None and dtheta.numel() < G * self.num_params():
+            raise ValueError("dtheta holds %d values, %d groups need %d" % (
+                dtheta.numel(), G, G * self.num_params()))
+        total = mem_row.numel() if mem_row is not None else 0
+        rc = self.lib.fia_group_influence(self.h, Q, _ptr(qu), _ptr(qi), _ptr(grp_offsets), G, _ptr(mem_offsets),
+                                          total, _ptr(mem_row), _ptr(group), _ptr(first_order), _ptr(dtheta),
+                                          _stream())
+        self._check(rc, "fia_group_influence")
 
     # ---- profiling ----
     def set_profiling(self, on, phases=None):

@@ -529,6 +529,77 @@ class GenericNeuralNet(object):
             out["topk_val"] = tv[:K].cpu().numpy()
         return out
 
+    def _checked_groups(self, n_queries, groups):
+        """Host validation of get_group_influence's groups (no GPU call): returns (grp_offsets
+        int64 [Q+1], mem_offsets int64 [G+1], mem_row int32 [total]) or raises ValueError."""
+        if len(groups) != n_queries:
+            raise ValueError("groups must hold one sequence of groups per test index (%d, got %d)" % (
+                n_queries, len(groups)))
+        n_train = int(self.num_train_examples)
+        grp_off, mem_off, rows = [0], [0], []
+        for per_query in groups:
+            for grp in per_query:
+                r = np.asarray(grp)
+                if r.size == 0:
+                    r = np.zeros(0, np.int64)
+                if r.ndim != 1:
+                    raise ValueError("a group must be a 1-d array of train rows")
+                if r.dtype.kind not in "iu":
+                    raise ValueError("train rows must be integers (got dtype %s)" % r.dtype)
+                r = r.astype(np.int64)
+                if r.size and (r.min() < 0 or r.max() >= n_train):
+                    raise ValueError("train rows must lie in [0, %d)" % n_train)
+                if np.unique(r).size != r.size:
+                    raise ValueError("a group lists a train row more than once")
+                rows.append(r)
+                mem_off.append(mem_off[-1] + r.size)
+            grp_off.append(len(mem_off) - 1)
+        mem_row = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+        return (np.asarray(grp_off, np.int64), np.asarray(mem_off, np.int64),
+                np.ascontiguousarray(mem_row, np.int32))
+
+    def get_group_influence(self, test_indices, groups, return_dtheta=False, inverse_hvp=None):
+        """Effect of removing SETS of training ratings on the predictions of test ratings (one
+        fia_group_influence call; the reference scores one rating at a time).  groups[q] is a
+        sequence of integer arrays of train rows, the groups of test rating test_indices[q]; it
+        may be empty, and so may a group.  For each group S
+
+            group       = v . (H - H_S)^-1 b_S      the system without S's ratings, solved again
+            first_order = (H^-1 v) . b_S            the sum of S's single-rating influences
+
+        (include/fia.h).  Sign convention: that of get_influence_on_test_loss -- the predicted
+        change of r-hat(u, i) when the ratings are removed.  A row that shares neither the test
+        rating's user nor its item contributes nothing; the test pair's own train row counts
+        twice, as in its related list.  inverse_hvp (float64 [Q, D], reference theta order), when
+        given, is only checked for its size: first_order always comes from the exact solve.
+        len(groups), integer rows, their range and duplicates inside a group are checked on the
+        host (ValueError) before any GPU call.  Returns dict(grp_offsets int64 [Q+1], mem_offsets
+        int64 [G+1], group float64 [G], first_order float64 [G], and with return_dtheta dtheta
+        float64 [G, D], the parameter step in the reference theta order) as numpy arrays."""
+        Q = len(test_indices)
+        grp_off, mem_off, mem_row = self._checked_groups(Q, groups)
+        D = self._host_num_params()
+        if inverse_hvp is not None and np.asarray(inverse_hvp).size != Q * D:
+            raise ValueError("inverse_hvp must hold %d x %d values" % (Q, D))
+        import torch
+        G = mem_off.size - 1
+        qu, qi = self._query_tensors(test_indices)
+        dev = self.ctx.torch_device
+        # (the count rejects query ids out of range and queries outside a prepare_for cover)
+        self.ctx.count_related(qu, qi)
+        d_go = torch.from_numpy(grp_off).to(dev)
+        d_mo = torch.from_numpy(mem_off).to(dev)
+        d_mr = torch.from_numpy(mem_row).to(dev) if mem_row.size else torch.empty(1, dtype=torch.int32, device=dev)[:0]
+        grp = torch.empty(max(G, 1), dtype=torch.float64, device=dev)
+        fo = torch.empty(max(G, 1), dtype=torch.float64, device=dev)
+        dth = torch.empty(max(G * D, 1), dtype=torch.float64, device=dev) if return_dtheta else None
+        self.ctx.group_influence(qu, qi, d_go, d_mo, d_mr, grp, fo, dth)
+        out = dict(grp_offsets=grp_off, mem_offsets=mem_off, group=grp[:G].cpu().numpy(),
+                   first_order=fo[:G].cpu().numpy())
+        if return_dtheta:
+            out["dtheta"] = dth[:G * D].cpu().numpy().reshape(G, D)
+        return out
+
     def _predict_device(self, qu, qi):
         """r-hat(u, i) in fp64 on the device from the uploaded (float32) parameter tables."""
         import torch

@@ -26,6 +26,8 @@
  *   (none: get_influence_on_test_loss asserts            fia_total_influence
  *     len(test_indices) == 1, mf:179 -- the influence of
  *     every train row on a SET of predictions)
+ *   (none: one row at a time is scored, mf:237-246 --    fia_group_influence
+ *     the effect of removing a SET of train rows)
  *
  * Conventions
  *   - All array arguments are DEVICE pointers owned by the caller (PyTorch).
@@ -263,6 +265,66 @@ int fia_total_influence(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user
                         double* total,            /* device [n_train], nullable                                  */
                         int32_t* count,           /* device [n_train], nullable                                  */
                         int K, int64_t* topk_idx, double* topk_val,   /* device [K], K in [0, FIA_MAX_TOPK]      */
+                        void* stream);
+
+/* Group removal influence: the predicted change of r-hat(u, i) when a SET of train rows is removed
+ * together, with the curvature that leaves with them (one Newton step of the restricted objective
+ * without those rows).  The reference has no counterpart: it scores one row at a time against the
+ * Hessian of the full related set (matrix_factorization.py:179, 237-246), and the sum of those
+ * scores under-predicts as the set grows -- H_t is a mean over only n_q related ratings.
+ * Query q = (q_user[q], q_item[q]) has n = n_q related ratings (with multiplicity, from the built
+ * index), theta_t in the reference order, v = d r-hat(u, i) / d theta_t and the assembled
+ *   H = (2/n) sum_rel (g g^T + e d2 r-hat) + wd * M + damping * I        as fia_query_batch solves it,
+ * M = [1]*2k + [0, 0] (MF) or all ones (NCF).  Its groups are g in [grp_offsets[q], grp_offsets[q+1]);
+ * the members of group g are the train rows mem_row[mem_offsets[g] .. mem_offsets[g+1]).  For a
+ * member j = (a, b, y):
+ *   m_j = [a == u] + [b == i]      how often j occurs in q's related list (fia_total_influence's
+ *                                  m_q(j): 2 for q's own pair, 0 for an unrelated row)
+ *   e_j = r-hat(a, b) - y          (current parameters, fp64)
+ *   g_j = d r-hat(a, b) / d theta_t   user-side blocks zero unless a == u, item-side unless b == i
+ *   C_j = d2 r-hat / d theta_u d theta_i, nonzero only when a == u and b == i: MF I on the
+ *         (p_u, q_i) cross block, NCF diag(W3g) on the (Pg_u, Qg_i) cross block
+ *   H_S = (1/n) sum_{j in S} m_j (2 g_j g_j^T + 2 e_j C_j + wd * M)
+ *   b_S = (1/n) sum_{j in S} m_j (2 e_j g_j + wd * M * theta_t)
+ *   dtheta[g*D ..) = (H - H_S)^-1 b_S     exact fp64 LDL^T of the full coupled D x D system
+ *   group[g]       = v . dtheta           predicted change of r-hat(u, i) when S is removed
+ *   first_order[g] = (H^-1 v) . b_S       = sum_{j in S} m_j * (the influence fia_query_batch writes for j)
+ * The normalisation stays 1 / n_q (removal is the -1/n up-weighting the influence uses), so with
+ * H_S dropped group equals first_order.
+ *   - An empty group, or one whose members all have m_j = 0, gives exactly +0.0 (group,
+ *     first_order, every dtheta entry); a member with m_j = 0 changes no bit of the result.
+ *   - A member listed twice is subtracted twice.
+ *   - A member row outside [0, n_train) is never used as an index: that group scores NaN, other
+ *     groups are unaffected.  n_q = 0, or a query id out of range (never used as an index), gives
+ *     NaN for all of the query's groups.
+ *   - If S removes every occurrence, H - H_S = damping * I and whatever the LDL^T gives is returned.
+ *   - Members are accumulated in list order, no floating-point atomics: the same inputs give the
+ *     same bits on every call, wherever the group and its query sit in the batch.
+ * group, first_order and dtheta may each be NULL; all three NULL is FIA_ERR_INVALID.
+ * grp_offsets[0] == 0, non-decreasing, grp_offsets[Q] == num_groups; mem_offsets likewise with
+ * total_members.  Needs params, index and a prepare (else FIA_ERR_STATE).  After fia_prepare_for
+ * the QUERIES must be covered, as for fia_query_batch; member rows may be any train row, and the
+ * results are bitwise those after fia_prepare.  Ordered on `stream`, no host synchronisation; it
+ * reads the entity Gram caches, so it joins a pending small-k Gram pass as fia_query_batch does
+ * (and, like it, cannot start a capture before that join).  num_queries == 0 or num_groups == 0
+ * returns FIA_OK and launches nothing.
+ * Batch limit: num_groups <= FIA_GROUP_MAX_GROUPS and total_members <= FIA_GROUP_MAX_MEMBERS
+ * (2^31 - 1 each): a larger batch is refused with FIA_ERR_INVALID before anything is reserved or
+ * launched -- split it.
+ * Sizes: MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32}, whose full packed system fits in LDS.
+ * The large-k models (MF k >= 128, NCF k >= 64) keep their systems in device memory: for them the
+ * call returns FIA_ERR_UNSUPPORTED. */
+#define FIA_GROUP_MAX_GROUPS ((1LL << 31) - 1)
+#define FIA_GROUP_MAX_MEMBERS ((1LL << 31) - 1)
+int fia_group_influence(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item,
+                        const int64_t* grp_offsets,  /* device [Q+1]: groups of query q                */
+                        int64_t num_groups,          /* == grp_offsets[Q]                              */
+                        const int64_t* mem_offsets,  /* device [G+1]: members of group g               */
+                        int64_t total_members,       /* == mem_offsets[G]                              */
+                        const int32_t* mem_row,      /* device [total_members]: train rows             */
+                        double* group,               /* device [G], nullable                           */
+                        double* first_order,         /* device [G], nullable                           */
+                        double* dtheta,              /* device [G*D], reference theta order, nullable  */
                         void* stream);
 
 /* Number of restricted parameters D of the registered model (0 if none). */
