@@ -594,6 +594,47 @@ int fia_group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t*
   })
 }
 
+int fia_self_influence(fia_ctx* c, int64_t num_rows, const int32_t* rows, double* first_order, double* newton,
+                       double* error, int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    // the batch bound comes first: nothing of an oversized batch is looked at
+    if (num_rows < 0 || num_rows > FIA_SELF_MAX_ROWS)
+      return fail(c, FIA_ERR_INVALID, "num_rows out of range [0, 2^31 - 1]: split the batch");
+    if (!c->p.valid || !c->idx.valid) return fail(c, FIA_ERR_STATE, "params/index missing");
+    if (!c->prepared) return fail(c, FIA_ERR_STATE, "fia_prepare has not been called since params/index changed");
+    if (c->subset || c->small_subset)
+      return fail(c, FIA_ERR_STATE,
+                  "fia_self_influence needs the caches of every entity: the last prepare was fia_prepare_for "
+                  "(a partial cover); call fia_prepare");
+    if (K < 0 || K > FIA_MAX_TOPK) return fail(c, FIA_ERR_INVALID, "K must be in [0, FIA_MAX_TOPK]");
+    if (K > 0 && (!topk_pos || !topk_idx || !topk_val)) return fail(c, FIA_ERR_INVALID, "null top-K output");
+    if (!first_order && !newton && !error && K == 0)
+      return fail(c, FIA_ERR_INVALID, "no output requested (first_order, newton, error, top-K)");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (num_rows == 0) {
+      if (K == 0) return FIA_OK;
+      if (int rc = enter_stream(c, s, "fia_self_influence"); rc != FIA_OK) return rc;
+      hipError_t e = fia::self_influence(c, 0, nullptr, nullptr, nullptr, nullptr, K, topk_pos, topk_idx, topk_val, s);
+      if (e != hipSuccess) return hip_fail(c, e, "fia_self_influence");
+      return FIA_OK;
+    }
+    if (!rows && num_rows != c->idx.N)
+      return fail(c, FIA_ERR_INVALID, "rows is NULL (every train row): num_rows must equal n_train");
+    if (!fia::group_supported(c->p.model, c->p.k))
+      return fail(c, FIA_ERR_UNSUPPORTED,
+                  "fia_self_influence is built for MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32} (the full "
+                  "packed system in LDS); the large-k models keep their systems in device memory");
+    if (int rc = enter_stream(c, s, "fia_self_influence"); rc != FIA_OK) return rc;
+    // the Gram caches of a pending small-k pass are read: join it, as fia_group_influence does
+    if (hipError_t es = fia::join_prepare(c, s); es != hipSuccess) return hip_fail(c, es, "fia_self_influence");
+    hipError_t e = fia::self_influence(c, num_rows, rows, first_order, newton, error, K, topk_pos, topk_idx, topk_val, s);
+    if (e != hipSuccess) return hip_fail(c, e, "fia_self_influence");
+    return FIA_OK;
+  })
+}
+
 int fia_set_profiling(fia_ctx* c, int phase_mask) {
   if (!c) return FIA_ERR_INVALID;
   c->profiling = (unsigned)phase_mask & ((1u << FIA_NUM_PHASES) - 1u);

@@ -234,7 +234,8 @@ struct fia_ctx {
   // query) pairs, per-group aggregates, entity -> group, per-query / per-group words, sort scratch
   fia::DevBuf tkeys, tvals, tagg, tslot, tword, tsort;
   // fia_group_influence (group.hip): train row -> {user, item, rating, list position} (per index),
-  // and per batch the queries' x_q = H^-1 v [Q * D] for first_order
+  // and per batch the queries' x_q = H^-1 v [Q * D] for first_order (fia_self_influence, self.hip:
+  // the same row table, and gxq for the newton values [num_rows] of a top-K without the array)
   fia::DevBuf rowrec, gxq;
   uint64_t rowrec_version = ~0ull;
   // large-k path (bigk.hip): per-list-position entity, per-train-row residual / NCF backward
@@ -403,6 +404,14 @@ hipError_t group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32
                            int64_t num_groups, const int64_t* mem_offsets, int64_t total_members,
                            const int32_t* mem_row, double* group, double* first_order, double* dtheta,
                            hipStream_t s);
+
+// fia_self_influence (self.hip): every listed train row against its own prediction, the group
+// call's singleton case fused; the sizes of group_supported; scratch: c->rowrec, c->cand_pos,
+// c->cand_val, and c->gxq for the newton values when only their top-K is asked for.  n == 0
+// only fills the top-K slots.
+hipError_t self_influence(fia_ctx* c, int64_t n, const int32_t* rows, double* first_order, double* newton,
+                          double* error, int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val,
+                          hipStream_t s);
 
 // phase event helpers (no-ops unless profiling)
 void phase_begin(fia_ctx* c, int phase, hipStream_t s);

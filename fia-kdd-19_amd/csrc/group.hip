@@ -57,23 +57,6 @@ __global__ void k_row_rec(int64_t N, int64_t U, const int64_t* __restrict__ ptr,
   rec[row[g]] = make_int4((int)lo, other[g], __float_as_int(rating[g]), (int)g);
 }
 
-// ids in range and related count of query (u, i); 0 for an id out of range (never an index)
-__device__ __forceinline__ int64_t related_count(const QueryArgs& A, int32_t u, int32_t i) {
-  if (!(u >= 0 && u < A.U && i >= 0 && i < A.I)) return 0;
-  return (A.ptr[0][u + 1] - A.ptr[0][u]) + (A.ptr[1][i + 1] - A.ptr[1][i]);
-}
-
-template <class M>
-__device__ __forceinline__ void stage_ncf(const QueryArgs& A, NCFWeights<M::ncf ? M::K : 2>& w, double* sW1,
-                                          double* sb1) {
-  if constexpr (M::ncf) {
-    constexpr int K = M::K;
-    load_ncf_weights<K>(w, A.t[6], A.t[7], A.t[8]);
-    for (int t = threadIdx.x; t < 2 * K * K; t += blockDim.x) sW1[t] = (double)A.t[4][t];
-    for (int t = threadIdx.x; t < K; t += blockDim.x) sb1[t] = (double)A.t[5][t];
-  }
-}
-
 // x_q = H^-1 v of every query with n_q > 0 (the others' slots are never read)
 template <class M>
 __global__ __launch_bounds__(kSolveThreads) void k_group_x(QueryArgs A, GroupArgs Gr) {
@@ -223,22 +206,10 @@ constexpr int64_t group_lds_bytes() {
 template <class M>
 hipError_t group_impl(fia_ctx* c, const QueryArgs& A, GroupArgs Gr, hipStream_t s) {
   constexpr int D = M::D;
-  const int64_t N = c->idx.N;
-  if (c->rowrec_version != c->idx.version) {
-    FIA_HIP_TRY(c->rowrec.reserve(sizeof(int4) * (size_t)(N > 0 ? N : 1), s));
-    if (N > 0) {
-      hipLaunchKernelGGL(k_row_rec, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, N, A.U, A.ptr[0], A.row[0],
-                         A.other[0], A.rating[0], c->rowrec.as<int4>());
-      FIA_HIP_TRY(hipGetLastError());
-    }
-    c->rowrec_version = c->idx.version;
-  }
+  FIA_HIP_TRY(ensure_rowrec(c, s));
   Gr.rowrec = c->rowrec.as<int4>();
-  // persistent workgroups (NCF weights staged once each), as many per CU as their LDS lets be
-  // resident (160 KB per CU, at most 16 one-wave workgroups: 4 waves per SIMD at <= 128 VGPRs)
-  constexpr int64_t lds = group_lds_bytes<M>();
-  constexpr int64_t per_cu = 160 * 1024 / lds < 1 ? 1 : (160 * 1024 / lds > 16 ? 16 : 160 * 1024 / lds);
-  const int64_t cap = (int64_t)(c->num_cus > 0 ? c->num_cus : 256) * per_cu;
+  // persistent workgroups (NCF weights staged once each), as many as their LDS lets be resident
+  const int64_t cap = solve_grid_cap(c, group_lds_bytes<M>());
   if (Gr.first) {
     FIA_HIP_TRY(c->gxq.reserve(sizeof(double) * (size_t)(Gr.Q * D), s));
     Gr.xq = c->gxq.as<double>();
@@ -251,18 +222,7 @@ hipError_t group_impl(fia_ctx* c, const QueryArgs& A, GroupArgs Gr, hipStream_t 
 
 }  // namespace
 
-bool group_supported(int model, int k) {
-  return (model == FIA_MODEL_MF && (k == 8 || k == 16 || k == 32 || k == 64)) ||
-         (model == FIA_MODEL_NCF && (k == 8 || k == 16 || k == 32));
-}
-
-hipError_t group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* grp_offsets,
-                           int64_t num_groups, const int64_t* mem_offsets, int64_t total_members,
-                           const int32_t* mem_row, double* group, double* first_order, double* dtheta,
-                           hipStream_t s) {
-  QueryArgs A{};
-  A.qu = qu;
-  A.qi = qi;
+void solve_query_args(const fia_ctx* c, QueryArgs& A) {
   A.U = c->p.U;
   A.I = c->p.I;
   for (int sd = 0; sd < 2; ++sd) {
@@ -281,6 +241,36 @@ hipError_t group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32
   A.pairs.sum = c->idx.psum.as<double>();
   A.pairs.mask = (unsigned long long)(c->idx.pcap - 1);
   A.N = c->idx.N;
+}
+
+hipError_t ensure_rowrec(fia_ctx* c, hipStream_t s) {
+  if (c->rowrec_version == c->idx.version) return hipSuccess;
+  const int64_t N = c->idx.N;
+  FIA_HIP_TRY(c->rowrec.reserve(sizeof(int4) * (size_t)(N > 0 ? N : 1), s));
+  if (N > 0) {
+    const Side& us = c->idx.side[0];
+    hipLaunchKernelGGL(k_row_rec, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, N, (int64_t)c->p.U,
+                       us.ptr.as<int64_t>(), us.row.as<int32_t>(), us.other.as<int32_t>(), us.rating.as<float>(),
+                       c->rowrec.as<int4>());
+    FIA_HIP_TRY(hipGetLastError());
+  }
+  c->rowrec_version = c->idx.version;
+  return hipSuccess;
+}
+
+bool group_supported(int model, int k) {
+  return (model == FIA_MODEL_MF && (k == 8 || k == 16 || k == 32 || k == 64)) ||
+         (model == FIA_MODEL_NCF && (k == 8 || k == 16 || k == 32));
+}
+
+hipError_t group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* grp_offsets,
+                           int64_t num_groups, const int64_t* mem_offsets, int64_t total_members,
+                           const int32_t* mem_row, double* group, double* first_order, double* dtheta,
+                           hipStream_t s) {
+  QueryArgs A{};
+  solve_query_args(c, A);
+  A.qu = qu;
+  A.qi = qi;
   GroupArgs Gr{};
   Gr.Q = Q;
   Gr.G = num_groups;

@@ -199,6 +199,85 @@ __device__ void block_topk(const double (&ca)[NC], const int (&cp)[NC], const do
   }
 }
 
+// One level of a batch-wide top-K merge (fia_total_influence, fia_self_influence): workgroup g
+// selects the K best of slots [g * FAN, (g + 1) * FAN) of `n_slots` (K entries each, position
+// -1 = none) into slot g of the next level, or, on the last level (one workgroup), into the
+// call's outputs.  Selection only: no value is changed on the way.
+template <int FAN>
+__global__ __launch_bounds__(256) void k_topk_merge(int64_t n_slots, int K, const int32_t* __restrict__ in_pos,
+                                                    const double* __restrict__ in_val,
+                                                    int32_t* __restrict__ out_pos, double* __restrict__ out_val,
+                                                    int64_t* __restrict__ topk_idx, double* __restrict__ topk_val) {
+  __shared__ double s_a[4], s_v[4];
+  __shared__ int s_p[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t s0 = (int64_t)blockIdx.x * FAN;
+  const int64_t s1 = s0 + FAN < n_slots ? s0 + FAN : n_slots;
+  const int64_t ncand = (s1 > s0 ? s1 - s0 : 0) * K;
+  const int32_t* __restrict__ cp = in_pos + s0 * K;
+  const double* __restrict__ cv = in_val + s0 * K;
+  double pa = INFINITY;
+  int pp = -1;
+  for (int t = 0; t < K; ++t) {
+    double ba = -2.0, bv = 0.0;
+    int bp = 0x7fffffff;
+    for (int64_t j = tid; j < ncand; j += 256) {
+      const int p = cp[j];
+      if (p < 0) continue;
+      const double val = cv[j];
+      const double a = topk_key(val);
+      if (better(pa, pp, a, p) && better(a, p, ba, bp)) { ba = a; bp = p; bv = val; }
+    }
+    wave_best(ba, bp, bv);
+    if (lane == 0) { s_a[wave] = ba; s_p[wave] = bp; s_v[wave] = bv; }
+    __syncthreads();
+    ba = s_a[0]; bp = s_p[0]; bv = s_v[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w)
+      if (better(s_a[w], s_p[w], ba, bp)) { ba = s_a[w]; bp = s_p[w]; bv = s_v[w]; }
+    __syncthreads();
+    if (tid == 0) {
+      const bool ok = ba > -1.5;
+      if (topk_idx) {
+        topk_idx[t] = ok ? (int64_t)bp : -1;
+        topk_val[t] = ok ? bv : NAN;
+      } else {
+        out_pos[(int64_t)blockIdx.x * K + t] = ok ? bp : -1;
+        out_val[(int64_t)blockIdx.x * K + t] = ok ? bv : NAN;
+      }
+    }
+    pa = ba;
+    pp = bp;
+  }
+}
+
+// Slots (of K entries) that the levels of a merge of `first` slots need, the first level included:
+// first + first / FAN + first / FAN^2 + ...
+template <int FAN>
+inline size_t topk_merge_slots(int64_t first) {
+  return (size_t)(first + first / (FAN - 1) + 8);
+}
+
+// Every level of the merge: `n` slots at the start of pos / val (topk_merge_slots<FAN>(n) slots
+// reserved), level by level behind them, down to the call's outputs [K]; n == 0 fills them with
+// -1 / NaN.
+template <int FAN>
+inline hipError_t topk_merge_levels(int64_t n, int K, int32_t* pos, double* val, int64_t* topk_idx, double* topk_val,
+                                    hipStream_t s) {
+  int64_t base = 0;
+  for (;;) {
+    const int64_t ng = n > 0 ? (n + FAN - 1) / FAN : 1;
+    const bool last = ng == 1;
+    hipLaunchKernelGGL(k_topk_merge<FAN>, dim3((unsigned)ng), dim3(256), 0, s, n, K, pos + base * K, val + base * K,
+                       pos + (base + n) * K, val + (base + n) * K, last ? topk_idx : nullptr,
+                       last ? topk_val : nullptr);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    if (last) return hipSuccess;
+    base += n;
+    n = ng;
+  }
+}
+
 // ------------------------------------------------------------------------------------
 // NCF helpers (NCF.py:85-145): z1 = L1_self + L1_other + b1 given; returns r-hat
 // pieces via the per-row MLP with the ReLU derivative 1[z > 0] (TF ReluGrad).

@@ -1,5 +1,6 @@
 // Device code of the full-D per-query system, shared by models.hip (k_solve, k_record_x and
-// the side-system solves' prologue) and group.hip (fia_group_influence): the LDS LDL^T, the
+// the side-system solves' prologue), group.hip (fia_group_influence) and self.hip
+// (fia_self_influence): the LDS LDL^T, the
 // query prologue (theta_t, v = d r-hat / d theta_t, r-hat of one pair) and the assembly of the
 // packed coupled Hessian from the two entity Gram caches.  One wave (kSolveThreads) per system
 // unless a function says otherwise.
@@ -171,6 +172,37 @@ __device__ __forceinline__ bool assemble_hessian(const QueryArgs& A, int32_t u, 
     H[t] = h;
   }
   return coupled;
+}
+
+// ids in range and related count of query (u, i); 0 for an id out of range (never an index)
+__device__ __forceinline__ int64_t related_count(const QueryArgs& A, int32_t u, int32_t i) {
+  if (!(u >= 0 && u < A.U && i >= 0 && i < A.I)) return 0;
+  return (A.ptr[0][u + 1] - A.ptr[0][u]) + (A.ptr[1][i + 1] - A.ptr[1][i]);
+}
+
+// the NCF weights solve_prologue reads, into the workgroup's LDS (once per persistent workgroup)
+template <class M>
+__device__ __forceinline__ void stage_ncf(const QueryArgs& A, NCFWeights<M::ncf ? M::K : 2>& w, double* sW1,
+                                          double* sb1) {
+  if constexpr (M::ncf) {
+    constexpr int K = M::K;
+    load_ncf_weights<K>(w, A.t[6], A.t[7], A.t[8]);
+    for (int t = threadIdx.x; t < 2 * K * K; t += blockDim.x) sW1[t] = (double)A.t[4][t];
+    for (int t = threadIdx.x; t < K; t += blockDim.x) sb1[t] = (double)A.t[5][t];
+  }
+}
+
+// ---- host side, shared by group.hip and self.hip (defined in group.hip) ----
+// the context's index, caches and parameters as the full-D kernels read them (qu / qi left null)
+void solve_query_args(const fia_ctx* c, QueryArgs& A);
+// c->rowrec: train row -> {user, item, rating bits, user-major list position}, built once per index
+hipError_t ensure_rowrec(fia_ctx* c, hipStream_t s);
+// one-wave workgroups of `lds` bytes that the device keeps resident (160 KB of LDS per CU, at most
+// 16 per CU: 4 waves per SIMD at <= 128 VGPRs): the grid of a persistent full-D kernel
+inline int64_t solve_grid_cap(const fia_ctx* c, int64_t lds) {
+  const int64_t fit = 160 * 1024 / lds;
+  const int64_t per_cu = fit < 1 ? 1 : (fit > 16 ? 16 : fit);
+  return (int64_t)(c->num_cus > 0 ? c->num_cus : 256) * per_cu;
 }
 
 }  // namespace fia

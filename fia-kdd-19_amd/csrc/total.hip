@@ -30,7 +30,7 @@
 //                  a single writer per row), tiles of kTotalTile positions: e_j and the dots as
 //                  fia_score_candidates computes them (coop_dots / cand_core_ncf), the per-query
 //                  vectors replaced by the two entities' aggregates; with top-K the tile's K best
-//   k_total_merge  K-round selection over groups of kTotalFan slots, level by level
+//   k_topk_merge   (kern.h) K-round selection over groups of kTotalFan slots, level by level
 // No floating-point atomics anywhere.
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -304,56 +304,6 @@ __global__ __launch_bounds__(kTotalTile) void k_total_rows(TotalArgs A, double* 
   }
 }
 
-// One level of the top-K merge: workgroup g selects the K best of slots [g * kTotalFan,
-// (g + 1) * kTotalFan) of `n_slots` (K entries each, position -1 = none) into slot g of the
-// next level, or, on the last level (one workgroup), into the call's outputs.
-__global__ __launch_bounds__(256) void k_total_merge(int64_t n_slots, int K, const int32_t* __restrict__ in_pos,
-                                                     const double* __restrict__ in_val,
-                                                     int32_t* __restrict__ out_pos, double* __restrict__ out_val,
-                                                     int64_t* __restrict__ topk_idx, double* __restrict__ topk_val) {
-  __shared__ double s_a[4], s_v[4];
-  __shared__ int s_p[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t s0 = (int64_t)blockIdx.x * kTotalFan;
-  const int64_t s1 = s0 + kTotalFan < n_slots ? s0 + kTotalFan : n_slots;
-  const int64_t ncand = (s1 > s0 ? s1 - s0 : 0) * K;
-  const int32_t* __restrict__ cp = in_pos + s0 * K;
-  const double* __restrict__ cv = in_val + s0 * K;
-  double pa = INFINITY;
-  int pp = -1;
-  for (int t = 0; t < K; ++t) {
-    double ba = -2.0, bv = 0.0;
-    int bp = 0x7fffffff;
-    for (int64_t j = tid; j < ncand; j += 256) {
-      const int p = cp[j];
-      if (p < 0) continue;
-      const double val = cv[j];
-      const double a = topk_key(val);
-      if (better(pa, pp, a, p) && better(a, p, ba, bp)) { ba = a; bp = p; bv = val; }
-    }
-    wave_best(ba, bp, bv);
-    if (lane == 0) { s_a[wave] = ba; s_p[wave] = bp; s_v[wave] = bv; }
-    __syncthreads();
-    ba = s_a[0]; bp = s_p[0]; bv = s_v[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-      if (better(s_a[w], s_p[w], ba, bp)) { ba = s_a[w]; bp = s_p[w]; bv = s_v[w]; }
-    __syncthreads();
-    if (tid == 0) {
-      const bool ok = ba > -1.5;
-      if (topk_idx) {
-        topk_idx[t] = ok ? (int64_t)bp : -1;
-        topk_val[t] = ok ? bv : NAN;
-      } else {
-        out_pos[(int64_t)blockIdx.x * K + t] = ok ? bp : -1;
-        out_val[(int64_t)blockIdx.x * K + t] = ok ? bv : NAN;
-      }
-    }
-    pa = ba;
-    pp = bp;
-  }
-}
-
 inline unsigned key_bits(int64_t n) {       // bits holding every key in [0, n]
   unsigned b = 1;
   while (b < 32 && ((int64_t)1 << b) <= n) ++b;
@@ -372,9 +322,7 @@ hipError_t total_impl(fia_ctx* c, TotalArgs A, double* total, int32_t* count, in
     if (total && N > 0) FIA_HIP_TRY(hipMemsetAsync(total, 0, sizeof(double) * (size_t)N, s));
     if (count && N > 0) FIA_HIP_TRY(hipMemsetAsync(count, 0, sizeof(int32_t) * (size_t)N, s));
     if (K > 0) {
-      hipLaunchKernelGGL(k_total_merge, dim3(1), dim3(256), 0, s, (int64_t)0, K, nullptr, nullptr, nullptr, nullptr,
-                         topk_idx, topk_val);
-      FIA_HIP_TRY(hipGetLastError());
+      FIA_HIP_TRY(topk_merge_levels<kTotalFan>(0, K, nullptr, nullptr, topk_idx, topk_val, s));
     }
     phase_end(c, 2, s);
     return hipSuccess;
@@ -406,7 +354,7 @@ hipError_t total_impl(fia_ctx* c, TotalArgs A, double* total, int32_t* count, in
   tb = c->tsort.bytes;
   if (K > 0) {
     // every level of the merge behind the tiles' slots: tiles + tiles / 64 + tiles / 64^2 + ...
-    const size_t slots = (size_t)(tiles + tiles / (kTotalFan - 1) + 8);
+    const size_t slots = topk_merge_slots<kTotalFan>(tiles);
     FIA_HIP_TRY(c->cand_pos.reserve(sizeof(int32_t) * slots * (size_t)K, s));
     FIA_HIP_TRY(c->cand_val.reserve(sizeof(double) * slots * (size_t)K, s));
   }
@@ -426,21 +374,8 @@ hipError_t total_impl(fia_ctx* c, TotalArgs A, double* total, int32_t* count, in
   phase_end(c, 2, s);
   if (K > 0) {
     phase_begin(c, 3, s);
-    int64_t n = tiles, base = 0;
-    for (;;) {
-      const int64_t ng = (n + kTotalFan - 1) / kTotalFan;
-      const bool last = ng == 1;
-      const int32_t* ip = c->cand_pos.as<int32_t>() + base * K;
-      const double* iv = c->cand_val.as<double>() + base * K;
-      int32_t* op = c->cand_pos.as<int32_t>() + (base + n) * K;
-      double* ov = c->cand_val.as<double>() + (base + n) * K;
-      hipLaunchKernelGGL(k_total_merge, dim3((unsigned)ng), dim3(256), 0, s, n, K, ip, iv, op, ov,
-                         last ? topk_idx : nullptr, last ? topk_val : nullptr);
-      FIA_HIP_TRY(hipGetLastError());
-      if (last) break;
-      base += n;
-      n = ng;
-    }
+    FIA_HIP_TRY(topk_merge_levels<kTotalFan>(tiles, K, c->cand_pos.as<int32_t>(), c->cand_val.as<double>(), topk_idx,
+                                             topk_val, s));
     phase_end(c, 3, s);
   }
   return hipSuccess;

@@ -41,6 +41,7 @@ SIGNATURES = {
     "fia_score_candidates": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "fia_total_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "fia_group_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
+    "fia_self_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
     "fia_num_params": (ctypes.c_int, [_P]),
     "fia_set_profiling": (ctypes.c_int, [_P, ctypes.c_int]),
     "fia_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I64)]),
@@ -315,6 +316,40 @@ class Context(object):
                                           total, _ptr(mem_row), _ptr(group), _ptr(first_order), _ptr(dtheta),
                                           _stream())
         self._check(rc, "fia_group_influence")
+
+    def self_influence(self, rows=None, first_order=None, newton=None, error=None, K=0, topk_pos=None,
+                       topk_idx=None, topk_val=None):
+        """fia_self_influence: for every train row listed in rows (int32; None = every row of the
+        built index, in order) its effect on its own prediction -- first_order, the sum of its two
+        influences in its own related list; newton, the same with the row's curvature taken out of
+        the system; error = r-hat - y (float64 [num_rows] each, any may be None) -- and with K
+        the K positions of largest |newton| (topk_pos / topk_idx int64 [K], topk_val float64
+        [K]).  A row outside [0, n_train) gives NaN."""
+        import torch
+        self._need_int32(rows, "rows")
+        n_train = getattr(self, "n_train", None)
+        if rows is None and n_train is None:
+            raise FIAError("self_influence(rows=None) needs a built index")
+        n = n_train if rows is None else rows.numel()
+        for t, name in ((first_order, "first_order"), (newton, "newton"), (error, "error"), (topk_val, "topk_val")):
+            if t is not None and t.dtype != torch.float64:
+                raise TypeError("%s must be a torch.float64 tensor" % name)
+        for t, name in ((topk_pos, "topk_pos"), (topk_idx, "topk_idx")):
+            if t is not None and t.dtype != torch.int64:
+                raise TypeError("%s must be a torch.int64 tensor" % name)
+        for t, name in ((rows, "rows"), (first_order, "first_order"), (newton, "newton"), (error, "error"),
+                        (topk_pos, "topk_pos"), (topk_idx, "topk_idx"), (topk_val, "topk_val")):
+            if t is not None and not (t.is_cuda and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous device (cuda) tensor" % name)
+        for t, name in ((first_order, "first_order"), (newton, "newton"), (error, "error")):
+            if t is not None and t.numel() < n:
+                raise ValueError("%s holds %d values, the batch has %d rows" % (name, t.numel(), n))
+        if K and (topk_pos is None or topk_idx is None or topk_val is None
+                  or min(topk_pos.numel(), topk_idx.numel(), topk_val.numel()) < K):
+            raise ValueError("top-K outputs must hold K values")
+        rc = self.lib.fia_self_influence(self.h, n, _ptr(rows), _ptr(first_order), _ptr(newton), _ptr(error), int(K),
+                                         _ptr(topk_pos), _ptr(topk_idx), _ptr(topk_val), _stream())
+        self._check(rc, "fia_self_influence")
 
     # ---- profiling ----
     def set_profiling(self, on, phases=None):

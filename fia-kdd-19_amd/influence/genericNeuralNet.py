@@ -600,6 +600,71 @@ class GenericNeuralNet(object):
             out["dtheta"] = dth[:G * D].cpu().numpy().reshape(G, D)
         return out
 
+    def _checked_self_rows(self, train_indices, K, full):
+        """Host validation of get_self_influence (no GPU call): returns (rows, K) with rows the
+        int32 [n] train rows, or None for every train row, or raises ValueError."""
+        if isinstance(K, bool) or int(K) != K or not 0 <= int(K) <= _lib.FIA_MAX_TOPK:
+            raise ValueError("K must be in [0, %d]" % _lib.FIA_MAX_TOPK)
+        if not full and int(K) == 0:
+            raise ValueError("nothing to return: full=False needs K > 0")
+        if train_indices is None:
+            return None, int(K)
+        r = np.asarray(train_indices)
+        if r.size == 0:
+            r = np.zeros(0, np.int64)
+        if r.ndim != 1:
+            raise ValueError("train_indices must be a 1-d array of train rows")
+        if r.dtype.kind not in "iu":
+            raise ValueError("train rows must be integers (got dtype %s)" % r.dtype)
+        n_train = int(self.num_train_examples)
+        if r.size and (r.min() < 0 or r.max() >= n_train):
+            raise ValueError("train rows must lie in [0, %d)" % n_train)
+        return np.ascontiguousarray(r, np.int32), int(K)
+
+    def get_self_influence(self, train_indices=None, K=0, full=True):
+        """Self-influence (leverage) of training ratings: the effect of each listed rating on its
+        OWN prediction (one fia_self_influence call; the scan for noisy or injected ratings).
+        For train row j = (a, b, y), with the system of the query (a, b):
+
+            first_order = (H^-1 v) . b_j            the sum of j's two influences in its own related list
+            newton      = v . (H - H_j)^-1 b_j      the system without j's curvature, solved again
+            error       = r-hat(a, b) - y
+
+        (include/fia.h; get_group_influence of the pair (a, b) with the single group {j}).  Sign
+        convention: that of get_influence_on_test_loss -- the predicted change of r-hat(a, b)
+        when the rating is removed.  The self-influence on the row's own squared error
+        (r-hat - y)^2 is 2 * error * newton.
+        train_indices: integer train rows (1-d, in [0, num_train_examples), duplicates allowed),
+        or None for every train row in order.  K in [0, FIA_MAX_TOPK]: also the K positions of
+        largest |newton| (ties to the lower position).  These, and full=False with K == 0, are
+        checked on the host (ValueError) before any GPU call.  Needs a full prepare (not
+        prepare_for).  Returns numpy arrays: with full dict(rows int64 [n], first_order, newton,
+        error float64 [n]); with K topk_pos int64 [K] (position in train_indices), topk_idx int64
+        [K] (train row), topk_val float64 [K] (signed newton), -1 / -1 / NaN in unused slots."""
+        rows, K = self._checked_self_rows(train_indices, K, full)
+        import torch
+        dev = self.ctx.torch_device
+        n = self.ctx.n_train if rows is None else rows.size
+        d_rows = None
+        if rows is not None:
+            d_rows = torch.from_numpy(rows).to(dev) if n else torch.empty(1, dtype=torch.int32, device=dev)[:0]
+        f64 = lambda m: torch.empty(max(m, 1), dtype=torch.float64, device=dev)
+        i64 = lambda m: torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+        fo, nw, er = (f64(n), f64(n), f64(n)) if full else (None, None, None)
+        tp, ti, tv = (i64(K), i64(K), f64(K)) if K else (None, None, None)
+        self.ctx.self_influence(d_rows, fo, nw, er, K, tp, ti, tv)
+        out = {}
+        if full:
+            out["rows"] = np.arange(n, dtype=np.int64) if rows is None else rows.astype(np.int64)
+            out["first_order"] = fo[:n].cpu().numpy()
+            out["newton"] = nw[:n].cpu().numpy()
+            out["error"] = er[:n].cpu().numpy()
+        if K:
+            out["topk_pos"] = tp[:K].cpu().numpy()
+            out["topk_idx"] = ti[:K].cpu().numpy()
+            out["topk_val"] = tv[:K].cpu().numpy()
+        return out
+
     def _predict_device(self, qu, qi):
         """r-hat(u, i) in fp64 on the device from the uploaded (float32) parameter tables."""
         import torch

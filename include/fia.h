@@ -28,6 +28,9 @@
  *     every train row on a SET of predictions)
  *   (none: one row at a time is scored, mf:237-246 --    fia_group_influence
  *     the effect of removing a SET of train rows)
+ *   (none: one test point per call, mf:179 -- every      fia_self_influence
+ *     train row's effect on its OWN prediction, the
+ *     leverage scan for suspicious ratings)
  *
  * Conventions
  *   - All array arguments are DEVICE pointers owned by the caller (PyTorch).
@@ -326,6 +329,58 @@ int fia_group_influence(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user
                         double* first_order,         /* device [G], nullable                           */
                         double* dtheta,              /* device [G*D], reference theta order, nullable  */
                         void* stream);
+
+/* Self-influence: the effect of a train rating on its OWN prediction (its leverage), for every
+ * listed train row in one fused pass -- the scan that finds noisy or injected ratings, and what
+ * turns a leave-one-out residual into a Cook's-distance style score.  The reference has no
+ * counterpart: it scores one test point per call (matrix_factorization.py:179).
+ * For position p with train row j = rows[p] = (a, b, y) the query is (a, b):
+ *   n       = |R_a| + |C_b| >= 2, theta_t, v = d r-hat(a, b) / d theta_t and the assembled H exactly
+ *             as fia_query_batch builds them; M and C as in fia_group_influence
+ *   e       = r-hat(a, b) - y
+ *   b_j     = (2/n) (2 e v + wd * M * theta_t)          row j occurs twice in its own related list: m_j = 2
+ *   H_j     = (2/n) (2 v v^T + 2 e C + wd * M)
+ *   first_order[p] = (H^-1 v) . b_j        the sum of the two influences fia_query_batch writes for j
+ *   newton[p]      = v . (H - H_j)^-1 b_j  one Newton step of the objective without row j: the
+ *                                          predicted change of r-hat(a, b) when the rating is removed
+ *   error[p]       = e
+ * This equals fia_group_influence for query (a, b) with the single group {j} (its first_order and
+ * group outputs; see the definitions there), without the index arrays, the second prologue and the
+ * Q * D scratch that call needs for it.  A pair present c times in train gives each of its rows
+ * m = 2 and its own y.  Rows are independent of one another; the same row listed twice in rows
+ * scores identically.
+ *   - A row outside [0, n_train) is never used as an index: its three outputs are NaN, its
+ *     neighbours are unaffected.
+ *   - No floating-point atomics: the same inputs give the same bits, wherever the row sits in rows
+ *     and whatever else is in the batch.
+ * topk (K in [0, FIA_MAX_TOPK]; 0 = off): the K positions of largest |newton| in fia_query_batch's
+ * order (|v| descending, ties: lower position first, NaN last), as position in rows (topk_pos),
+ * train row (topk_idx: the entry of rows as given) and signed newton (topk_val), device arrays [K];
+ * unused slots hold -1 / -1 / NaN.  It works with newton NULL (the values go to context scratch).
+ * first_order, newton and error may each be NULL (a solve nobody asked for is skipped); all three
+ * NULL with K == 0 is FIA_ERR_INVALID.  rows NULL means rows 0 .. n_train - 1, and then num_rows
+ * must equal n_train.  num_rows == 0 returns FIA_OK and launches nothing but the fill of the top-K
+ * slots.
+ * Batch limit: num_rows <= FIA_SELF_MAX_ROWS (2^31 - 1: the top-K keeps a 32-bit position): a larger
+ * batch is refused with FIA_ERR_INVALID before anything is reserved or launched -- split it.
+ * Needs params, index and a full fia_prepare (else FIA_ERR_STATE): after fia_prepare_for the call
+ * returns FIA_ERR_STATE -- a scan touches nearly every entity, a partial cover is the wrong tool.
+ * Ordered on `stream`, no host synchronisation; it reads the entity Gram caches, so it joins a
+ * pending small-k Gram pass as fia_group_influence does (and, like it, cannot start a capture
+ * before that join).  Checks run in fia_group_influence's order: bounds, state, outputs, the empty
+ * batch, nulls, support.
+ * Sizes: those of fia_group_influence (MF k in {8, 16, 32, 64}, NCF k in {8, 16, 32}); anything
+ * else is FIA_ERR_UNSUPPORTED. */
+#define FIA_SELF_MAX_ROWS ((1LL << 31) - 1)
+int fia_self_influence(fia_ctx* ctx,
+                       int64_t num_rows,
+                       const int32_t* rows,      /* device [num_rows] train rows; NULL = rows 0 .. n_train-1,
+                                                    and then num_rows must equal n_train                    */
+                       double* first_order,      /* device [num_rows], nullable */
+                       double* newton,           /* device [num_rows], nullable */
+                       double* error,            /* device [num_rows], nullable */
+                       int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val,   /* device [K] */
+                       void* stream);
 
 /* Number of restricted parameters D of the registered model (0 if none). */
 int fia_num_params(const fia_ctx* ctx);
