@@ -127,6 +127,13 @@ int fail(fia_ctx* c, int code, const std::string& msg) {
   return code;
 }
 
+// the state every call that reads the caches needs: parameters, index, and a prepare since either changed
+int check_prepared(fia_ctx* c) {
+  if (!c->p.valid || !c->idx.valid) return fail(c, FIA_ERR_STATE, "params/index missing");
+  if (!c->prepared) return fail(c, FIA_ERR_STATE, "fia_prepare has not been called since params/index changed");
+  return FIA_OK;
+}
+
 int hip_fail(fia_ctx* c, hipError_t e, const char* where) {
   return fail(c, FIA_ERR_HIP, std::string(where) + ": " + hipGetErrorString(e));
 }
@@ -440,8 +447,7 @@ static int query_batch_common(fia_ctx* c, int64_t Q, const int32_t* qu, const in
                               const double* x_in) {
   if (!c) return FIA_ERR_INVALID;
   FIA_GUARDED(c, {
-    if (!c->p.valid || !c->idx.valid) return fail(c, FIA_ERR_STATE, "params/index missing");
-    if (!c->prepared) return fail(c, FIA_ERR_STATE, "fia_prepare has not been called since params/index changed");
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
     if (Q < 0 || Q >= (1LL << 31)) return fail(c, FIA_ERR_INVALID, "num_queries out of range");
     if (total_rel < 0) return fail(c, FIA_ERR_INVALID, "total_rel < 0");
     if (K < 0 || K > FIA_MAX_TOPK) return fail(c, FIA_ERR_INVALID, "K must be in [0, FIA_MAX_TOPK]");
@@ -501,8 +507,7 @@ int fia_score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t
                          int64_t* topk_pos, double* topk_val, void* stream) {
   if (!c) return FIA_ERR_INVALID;
   FIA_GUARDED(c, {
-    if (!c->p.valid || !c->idx.valid) return fail(c, FIA_ERR_STATE, "params/index missing");
-    if (!c->prepared) return fail(c, FIA_ERR_STATE, "fia_prepare has not been called since params/index changed");
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
     if (Q < 0 || Q >= (1LL << 31)) return fail(c, FIA_ERR_INVALID, "num_queries out of range");
     if (total_cand < 0) return fail(c, FIA_ERR_INVALID, "total_cand < 0");
     // a candidate's position inside its query's list is kept in 32 bits by the top-K selection
@@ -523,10 +528,8 @@ int fia_score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t
     // first kernels: l1_ev; once that is joined on this stream nothing else is waited for)
     if (c->p.model == FIA_MODEL_NCF && c->l1_pending)
       if (hipError_t es = fia::join_l1(c, s); es != hipSuccess) return hip_fail(c, es, "fia_score_candidates");
-    bool unsup = false;
     hipError_t e = fia::score_candidates(c, Q, qu, qi, x, cand_offsets, total_cand, cand_user, cand_item,
-                                         cand_rating, influence, K, topk_pos, topk_val, s, unsup);
-    if (unsup) return fail(c, FIA_ERR_UNSUPPORTED, "model/k not supported");
+                                         cand_rating, influence, K, topk_pos, topk_val, s);
     if (e != hipSuccess) return hip_fail(c, e, "fia_score_candidates");
     return FIA_OK;
   })
@@ -539,8 +542,7 @@ int fia_total_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t*
     // the batch bound comes first: nothing of an oversized batch is looked at
     if (Q < 0 || Q > FIA_TOTAL_MAX_QUERIES)
       return fail(c, FIA_ERR_INVALID, "num_queries out of range [0, 2^30]: split the batch (totals add)");
-    if (!c->p.valid || !c->idx.valid) return fail(c, FIA_ERR_STATE, "params/index missing");
-    if (!c->prepared) return fail(c, FIA_ERR_STATE, "fia_prepare has not been called since params/index changed");
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
     if (K < 0 || K > FIA_MAX_TOPK) return fail(c, FIA_ERR_INVALID, "K must be in [0, FIA_MAX_TOPK]");
     if (K > 0 && (!topk_idx || !topk_val)) return fail(c, FIA_ERR_INVALID, "null top-K output");
     if (!total && !count && K == 0) return fail(c, FIA_ERR_INVALID, "no output requested (total, count, top-K)");
@@ -552,9 +554,7 @@ int fia_total_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t*
     // as fia_score_candidates: of a pending small-k Gram pass only the NCF layer-1 rows are read
     if (c->p.model == FIA_MODEL_NCF && c->l1_pending)
       if (hipError_t es = fia::join_l1(c, s); es != hipSuccess) return hip_fail(c, es, "fia_total_influence");
-    bool unsup = false;
-    hipError_t e = fia::total_influence(c, Q, qu, qi, x, total, count, K, topk_idx, topk_val, s, unsup);
-    if (unsup) return fail(c, FIA_ERR_UNSUPPORTED, "model/k not supported");
+    hipError_t e = fia::total_influence(c, Q, qu, qi, x, total, count, K, topk_idx, topk_val, s);
     if (e != hipSuccess) return hip_fail(c, e, "fia_total_influence");
     return FIA_OK;
   })
@@ -571,8 +571,7 @@ int fia_group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t*
       return fail(c, FIA_ERR_INVALID, "num_groups out of range [0, 2^31 - 1]: split the batch");
     if (total_members < 0 || total_members > FIA_GROUP_MAX_MEMBERS)
       return fail(c, FIA_ERR_INVALID, "total_members out of range [0, 2^31 - 1]: split the batch");
-    if (!c->p.valid || !c->idx.valid) return fail(c, FIA_ERR_STATE, "params/index missing");
-    if (!c->prepared) return fail(c, FIA_ERR_STATE, "fia_prepare has not been called since params/index changed");
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
     if (!group && !first_order && !dtheta)
       return fail(c, FIA_ERR_INVALID, "no output requested (group, first_order, dtheta)");
     if (Q == 0 || num_groups == 0) return FIA_OK;
@@ -601,8 +600,7 @@ int fia_self_influence(fia_ctx* c, int64_t num_rows, const int32_t* rows, double
     // the batch bound comes first: nothing of an oversized batch is looked at
     if (num_rows < 0 || num_rows > FIA_SELF_MAX_ROWS)
       return fail(c, FIA_ERR_INVALID, "num_rows out of range [0, 2^31 - 1]: split the batch");
-    if (!c->p.valid || !c->idx.valid) return fail(c, FIA_ERR_STATE, "params/index missing");
-    if (!c->prepared) return fail(c, FIA_ERR_STATE, "fia_prepare has not been called since params/index changed");
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
     if (c->subset || c->small_subset)
       return fail(c, FIA_ERR_STATE,
                   "fia_self_influence needs the caches of every entity: the last prepare was fia_prepare_for "

@@ -161,12 +161,7 @@ __global__ void k_check_cover(int64_t Q, const int32_t* __restrict__ qu, const i
 // ------------------------------------------------------------------------------------
 __global__ void k_self(int64_t N, int64_t n_ent, const int64_t* __restrict__ ptr, int32_t* __restrict__ self) {
   for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < N; p += (int64_t)gridDim.x * blockDim.x) {
-    int64_t lo = 0, hi = n_ent;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (ptr[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    self[p] = (int32_t)lo;
+    self[p] = (int32_t)last_at_most(ptr, (int64_t)0, n_ent, p);
   }
 }
 
@@ -1728,28 +1723,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 // ------------------------------------------------------------------------------------
 BigArgs make_big_args(fia_ctx* c, const int32_t* qu, const int32_t* qi) {
   BigArgs A;
+  fill_list_args(c, A);
   A.qu = qu;
   A.qi = qi;
-  A.U = c->p.U;
-  A.I = c->p.I;
   for (int s = 0; s < 2; ++s) {
-    A.ptr[s] = c->idx.side[s].ptr.as<int64_t>();
-    A.row[s] = c->idx.side[s].row.as<int32_t>();
-    A.other[s] = c->idx.side[s].other.as<int32_t>();
-    A.rating[s] = c->idx.side[s].rating.as<float>();
-    A.gram[s] = c->gram[s].as<double>();
-    A.l1[s] = c->l1[s].as<double>();
     A.gm[s] = c->gm[s].as<double>();
     A.slot[s] = c->subset ? c->slot[s].as<int32_t>() : nullptr;
   }
   A.resid = c->resid.as<double>();
-  for (int t = 0; t < 10; ++t) A.t[t] = c->p.t[t];
-  A.wd = c->p.wd;
-  A.damping = c->p.damping;
-  A.pairs.key = c->idx.pkey.as<unsigned long long>();
-  A.pairs.cnt = c->idx.pcnt.as<int32_t>();
-  A.pairs.sum = c->idx.psum.as<double>();
-  A.pairs.mask = (unsigned long long)(c->idx.pcap - 1);
   return A;
 }
 
@@ -2011,10 +1992,6 @@ hipError_t query_big_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_
 
 }  // namespace
 
-#define FIA_BIG_CASES(X) \
-  X(FIA_MODEL_MF, 128, BMF<128>) X(FIA_MODEL_MF, 256, BMF<256>) X(FIA_MODEL_NCF, 64, BNCF<64>) \
-  X(FIA_MODEL_NCF, 128, BNCF<128>) X(FIA_MODEL_NCF, 256, BNCF<256>)
-
 // per-list-position owning entity of both sides (rebuilt when the index changes)
 hipError_t ensure_self(fia_ctx* c, hipStream_t s) {
   const Index& X = c->idx;
@@ -2033,18 +2010,14 @@ hipError_t ensure_self(fia_ctx* c, hipStream_t s) {
 }
 
 bool big_supported(int model, int k) {
-#define X(m, kk, T) if (model == m && k == kk) return true;
-  FIA_BIG_CASES(X)
-#undef X
-  return false;
+  return for_big_size<BMF, BNCF>(model, k, [](auto) {});
 }
 
 hipError_t prepare_big(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, hipStream_t s) {
   c->small_subset = false;
-#define X(m, kk, T) if (c->p.model == m && c->p.k == kk) return prepare_big_impl<T>(c, Q, qu, qi, s);
-  FIA_BIG_CASES(X)
-#undef X
-  return hipErrorInvalidValue;
+  hipError_t e = hipErrorInvalidValue;
+  for_big_size<BMF, BNCF>(c->p.model, c->p.k, [&](auto m) { e = prepare_big_impl<decltype(m)>(c, Q, qu, qi, s); });
+  return e;
 }
 
 hipError_t check_cover(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, int32_t* flag, hipStream_t s) {
@@ -2057,13 +2030,12 @@ hipError_t check_cover(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* 
 hipError_t query_big(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* offsets,
                      int64_t max_chunks, int32_t* rel_idx, double* influence, double* x_out, int K,
                      int64_t* topk_pos, int64_t* topk_idx, double* topk_val, hipStream_t s, const double* x_in) {
-#define X(m, kk, T)                                                                                            \
-  if (c->p.model == m && c->p.k == kk)                                                                         \
-    return query_big_impl<T>(c, Q, qu, qi, offsets, max_chunks, rel_idx, influence, x_out, K, topk_pos, topk_idx, \
-                             topk_val, s, x_in);
-  FIA_BIG_CASES(X)
-#undef X
-  return hipErrorInvalidValue;
+  hipError_t e = hipErrorInvalidValue;
+  for_big_size<BMF, BNCF>(c->p.model, c->p.k, [&](auto m) {
+    e = query_big_impl<decltype(m)>(c, Q, qu, qi, offsets, max_chunks, rel_idx, influence, x_out, K, topk_pos,
+                                    topk_idx, topk_val, s, x_in);
+  });
+  return e;
 }
 
 }  // namespace fia

@@ -8,7 +8,8 @@
 //                 x_mlp . (W1_side d1) = y_side . d1) and W3g * x_gmf
 //   coop_dots     the three k-long dots of a pair, rows gathered cooperatively
 //   stage_z1 / cand_core_ncf   the NCF MLP forward and y . d1
-// `Args` is any struct with the tables t[10], the list pointers ptr[2], l1[2] and wd.
+// `Args` is any struct with the members of ModelArgs (common.h): the tables t[10], the list
+// pointers ptr[2], l1[2] and wd.
 #pragma once
 
 #include "kern.h"
@@ -21,12 +22,6 @@ template <class M>
 constexpr int cand_rec_size() {
   // {1 / n_q, c_q}; NCF: + y_user[K], y_item[K], W3g * x_Pg [K], W3g * x_Qg [K]
   return M::ncf ? 2 + 4 * M::K : 2;
-}
-
-__device__ __forceinline__ double cand_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
 }
 
 // The record of query (u, i) (ids in range) with inverse HVP xq (reference theta order), by
@@ -51,7 +46,7 @@ __device__ __forceinline__ void query_record(const Args& A, int32_t u, int32_t i
       part += xq[a] * (double)Pm[a] + xq[K + a] * (double)Qm[a] + xq[2 * K + a] * (double)Pg[a] +
               xq[3 * K + a] * (double)Qg[a];
   }
-  part = cand_wave_sum(part);
+  part = wave_sum(part);
   const double inv_n = 1.0 / (double)n;     // n_q = 0: inf, and x is NaN
   if (lane == 0) {
     Rq[0] = inv_n;

@@ -136,7 +136,44 @@ struct Index {
   bool valid = false;
 };
 
+// ---- the (model, k) sizes the library is built for, each spelled once ----
+// small k: every structure of a query fits a wave's registers or a workgroup's LDS (models.hip)
+#define FIA_SMALL_SIZES(X) X(MF, 8) X(MF, 16) X(MF, 32) X(MF, 64) X(NCF, 8) X(NCF, 16) X(NCF, 32)
+// large k (bigk.hip)
+#define FIA_BIG_SIZES(X) X(MF, 128) X(MF, 256) X(NCF, 64) X(NCF, 128) X(NCF, 256)
+
+// f(MF<k>{}) or f(NCF<k>{}) for the size (model, k) of a list, MF / NCF being the caller's trait
+// templates (MFm / NCFm of kern.h, BMF / BNCF of bigk.hip); false, and f not called, for a size
+// not in the list.  f's own result goes out through its captures.
+#define FIA_SIZE_CASE(fam, kv)                \
+  if (model == FIA_MODEL_##fam && k == kv) {  \
+    f(fam<kv>{});                             \
+    return true;                              \
+  }
+template <template <int> class MF, template <int> class NCF, class F>
+bool for_small_size(int model, int k, F&& f) {
+  FIA_SMALL_SIZES(FIA_SIZE_CASE)
+  return false;
+}
+template <template <int> class MF, template <int> class NCF, class F>
+bool for_big_size(int model, int k, F&& f) {
+  FIA_BIG_SIZES(FIA_SIZE_CASE)
+  return false;
+}
+#undef FIA_SIZE_CASE
+
 // ---- device helpers shared by the kernels ----
+// the largest e in [lo, hi] with off[e] <= g (off[lo] <= g given): the owner of position g in
+// ascending offsets
+template <class I, class T>
+__device__ __forceinline__ I last_at_most(const T* __restrict__ off, I lo, I hi, T g) {
+  while (lo < hi) {
+    const I mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= g) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 constexpr unsigned long long kEmptyKey = ~0ull;
 
 __host__ __device__ inline unsigned long long pair_hash(unsigned long long k) {
@@ -284,6 +321,51 @@ struct fia_ctx {
 
 namespace fia {
 
+// ---- the context as the kernels' argument structs carry it ----
+// What every kernel reads of the model: the table sizes, the list pointers, the parameter tables,
+// the dense NCF layer-1 rows and the weight decay.  The argument structs of the kernels that read
+// nothing else of the context (score_cand.hip, total.hip) derive from it; QueryArgs (kern.h) and
+// BigArgs (bigk.hip) hold the same members among their own, in the order their kernels were
+// tuned with (moving them changed the register counts of three solve kernels).
+struct ModelArgs {
+  int64_t U, I;
+  const int64_t* ptr[2];
+  const float* t[10];
+  const double* l1[2];
+  double wd;
+};
+template <class Args>
+void fill_model_args(const fia_ctx* c, Args& A) {
+  A.U = c->p.U;
+  A.I = c->p.I;
+  for (int s = 0; s < 2; ++s) {
+    A.ptr[s] = c->idx.side[s].ptr.as<int64_t>();
+    A.l1[s] = c->l1[s].as<double>();
+  }
+  for (int j = 0; j < 10; ++j) A.t[j] = c->p.t[j];
+  A.wd = c->p.wd;
+}
+
+inline PairTable pair_table(const Index& X) {
+  return {X.pkey.as<unsigned long long>(), X.pcnt.as<int32_t>(), X.psum.as<double>(),
+          (unsigned long long)(X.pcap - 1)};
+}
+
+// ... and what the per-list-position kernels read besides: the lists of both sides, the Gram
+// caches, the damping and the train-pair table
+template <class Args>
+void fill_list_args(const fia_ctx* c, Args& A) {
+  fill_model_args(c, A);
+  for (int s = 0; s < 2; ++s) {
+    A.row[s] = c->idx.side[s].row.as<int32_t>();
+    A.other[s] = c->idx.side[s].other.as<int32_t>();
+    A.rating[s] = c->idx.side[s].rating.as<float>();
+    A.gram[s] = c->gram[s].as<double>();
+  }
+  A.damping = c->p.damping;
+  A.pairs = pair_table(c->idx);
+}
+
 // ---- launchers implemented in the .hip units ----
 hipError_t build_index(fia_ctx* c, int64_t N, int64_t U, int64_t I, const int32_t* user,
                        const int32_t* item, const float* rating, hipStream_t s, std::string& why);
@@ -388,14 +470,14 @@ hipError_t launch_topk_merge(fia_ctx* c, int64_t Q, const int32_t* qu, const int
 hipError_t score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const double* x,
                             const int64_t* cand_offsets, int64_t total_cand, const int32_t* cand_user,
                             const int32_t* cand_item, const float* cand_rating, double* influence, int K,
-                            int64_t* topk_pos, double* topk_val, hipStream_t s, bool& unsupported);
+                            int64_t* topk_pos, double* topk_val, hipStream_t s);
 
 // fia_total_influence (total.hip): the scatter-add of fia_query_batch_x's influence by train
 // row, computed from per-entity aggregates of the queries; scratch: c->rec, c->cand_pos,
 // c->cand_val and the t* buffers
 hipError_t total_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const double* x,
                            double* total, int32_t* count, int K, int64_t* topk_idx, double* topk_val,
-                           hipStream_t s, bool& unsupported);
+                           hipStream_t s);
 
 // fia_group_influence (group.hip): per group of train rows the re-solved system with the
 // group's rows removed; small k only (group_supported); scratch: c->rowrec, c->gxq

@@ -49,11 +49,7 @@ __global__ void k_row_rec(int64_t N, int64_t U, const int64_t* __restrict__ ptr,
                           int4* __restrict__ rec) {
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= N) return;
-  int64_t lo = 0, hi = U - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (ptr[mid] <= g) lo = mid; else hi = mid - 1;
-  }
+  const int64_t lo = last_at_most(ptr, (int64_t)0, U - 1, g);
   rec[row[g]] = make_int4((int)lo, other[g], __float_as_int(rating[g]), (int)g);
 }
 
@@ -99,11 +95,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_group(QueryArgs A, GroupArgs 
   for (int64_t gi = blockIdx.x; gi < Gr.G; gi += gridDim.x) {
     __syncthreads();
     // the group's query: the largest q in [0, Q) with grp_off[q] <= gi
-    int64_t q = 0;
-    for (int64_t hi = Gr.Q - 1; q < hi;) {
-      const int64_t mid = (q + hi + 1) >> 1;
-      if (Gr.grp_off[mid] <= gi) q = mid; else hi = mid - 1;
-    }
+    const int64_t q = last_at_most(Gr.grp_off, (int64_t)0, Gr.Q - 1, gi);
     const int32_t u = A.qu[q], i = A.qi[q];
     const int64_t n = related_count(A, u, i);
     int64_t m0 = Gr.mem_off[gi], m1 = Gr.mem_off[gi + 1];
@@ -139,27 +131,9 @@ __global__ __launch_bounds__(kSolveThreads) void k_group(QueryArgs A, GroupArgs 
           for (int c = lane; c < Ds; c += kSolveThreads) gj[Ds + c] = 0.0;
         __syncthreads();
         const double mn = ((on_u ? 1.0 : 0.0) + (on_i ? 1.0 : 0.0)) * inv_n;    // m_j / n
-        const double s2 = 2.0 * mn;
-        // H -= (2 m_j / n) g_j g_j^T on the blocks where g_j is nonzero
-        const int r0 = on_u ? 0 : Ds, r1 = on_i ? D : Ds;
-        for (int r = r0; r < r1; ++r) {
-          const double gr = s2 * gj[r];
-          double* __restrict__ Hr = H + tri(r, 0);
-          for (int c = r0 + lane; c <= r; c += kSolveThreads) Hr[c] = fma(-gr, gj[c], Hr[c]);
-        }
-        // ... -= (2 m_j / n) e_j C_j: the own pair's coupling of the user and item blocks
-        if (on_u && on_i) {
-          for (int c = lane; c < K; c += kSolveThreads) {
-            if constexpr (!M::ncf) H[tri(Ds + c, c)] -= s2 * e;                         // I on (p_u, q_i)
-            else H[tri(Ds + K + c, K + c)] -= s2 * e * w.W3[K / 2 + c];                 // diag(W3g) on (Pg_u, Qg_i)
-          }
-        }
-        // ... -= (m_j / n) wd M, and b_S += (m_j / n) (2 e_j g_j + wd M theta_t)
-        for (int c = lane; c < D; c += kSolveThreads) {
-          const double dec = M::decayed(c < Ds ? c : c - Ds) ? A.wd : 0.0;
-          H[tri(c, c)] -= mn * dec;
-          bS[c] += mn * (2.0 * e * gj[c] + dec * th[c]);
-        }
+        // H -= the member's terms, g_j g_j^T on the blocks where g_j is nonzero; b_S += its gradient
+        remove_member<M>(H, gj, e, mn, on_u ? 0 : Ds, on_i ? D : Ds, on_u && on_i, w, A.wd);
+        for (int c = lane; c < D; c += kSolveThreads) bS[c] += member_rhs<M>(c, gj, th, e, mn, A.wd);
       }
       __syncthreads();
     }
@@ -222,27 +196,6 @@ hipError_t group_impl(fia_ctx* c, const QueryArgs& A, GroupArgs Gr, hipStream_t 
 
 }  // namespace
 
-void solve_query_args(const fia_ctx* c, QueryArgs& A) {
-  A.U = c->p.U;
-  A.I = c->p.I;
-  for (int sd = 0; sd < 2; ++sd) {
-    A.ptr[sd] = c->idx.side[sd].ptr.as<int64_t>();
-    A.row[sd] = c->idx.side[sd].row.as<int32_t>();
-    A.other[sd] = c->idx.side[sd].other.as<int32_t>();
-    A.rating[sd] = c->idx.side[sd].rating.as<float>();
-    A.gram[sd] = c->gram[sd].as<double>();
-    A.l1[sd] = c->l1[sd].as<double>();
-  }
-  for (int t = 0; t < 10; ++t) A.t[t] = c->p.t[t];
-  A.wd = c->p.wd;
-  A.damping = c->p.damping;
-  A.pairs.key = c->idx.pkey.as<unsigned long long>();
-  A.pairs.cnt = c->idx.pcnt.as<int32_t>();
-  A.pairs.sum = c->idx.psum.as<double>();
-  A.pairs.mask = (unsigned long long)(c->idx.pcap - 1);
-  A.N = c->idx.N;
-}
-
 hipError_t ensure_rowrec(fia_ctx* c, hipStream_t s) {
   if (c->rowrec_version == c->idx.version) return hipSuccess;
   const int64_t N = c->idx.N;
@@ -259,18 +212,14 @@ hipError_t ensure_rowrec(fia_ctx* c, hipStream_t s) {
 }
 
 bool group_supported(int model, int k) {
-  return (model == FIA_MODEL_MF && (k == 8 || k == 16 || k == 32 || k == 64)) ||
-         (model == FIA_MODEL_NCF && (k == 8 || k == 16 || k == 32));
+  return dispatch_small(model, k, [](auto) {});
 }
 
 hipError_t group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* grp_offsets,
                            int64_t num_groups, const int64_t* mem_offsets, int64_t total_members,
                            const int32_t* mem_row, double* group, double* first_order, double* dtheta,
                            hipStream_t s) {
-  QueryArgs A{};
-  solve_query_args(c, A);
-  A.qu = qu;
-  A.qi = qi;
+  const QueryArgs A = make_args(c, qu, qi);
   GroupArgs Gr{};
   Gr.Q = Q;
   Gr.G = num_groups;
@@ -281,17 +230,9 @@ hipError_t group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32
   Gr.group = group;
   Gr.first = first_order;
   Gr.dtheta = dtheta;
-#define FIA_GROUP_CASE(MODEL, KV, T) \
-  if (c->p.model == MODEL && c->p.k == KV) return group_impl<T<KV>>(c, A, Gr, s);
-  FIA_GROUP_CASE(FIA_MODEL_MF, 8, MFm)
-  FIA_GROUP_CASE(FIA_MODEL_MF, 16, MFm)
-  FIA_GROUP_CASE(FIA_MODEL_MF, 32, MFm)
-  FIA_GROUP_CASE(FIA_MODEL_MF, 64, MFm)
-  FIA_GROUP_CASE(FIA_MODEL_NCF, 8, NCFm)
-  FIA_GROUP_CASE(FIA_MODEL_NCF, 16, NCFm)
-  FIA_GROUP_CASE(FIA_MODEL_NCF, 32, NCFm)
-#undef FIA_GROUP_CASE
-  return hipErrorInvalidValue;      // (group_supported is checked by the caller)
+  hipError_t e = hipErrorInvalidValue;      // (group_supported is checked by the caller)
+  dispatch_small(c->p.model, c->p.k, [&](auto m) { e = group_impl<decltype(m)>(c, A, Gr, s); });
+  return e;
 }
 
 }  // namespace fia

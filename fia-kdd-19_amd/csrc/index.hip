@@ -332,12 +332,7 @@ __global__ __launch_bounds__(kScanThreads) void k_query_scan(
       for (int64_t c = dstart + threadIdx.x; c < dend; c += kScanThreads) {
         // the owner: the last thread whose start is <= c (starts ascend; a thread with no
         // descriptors shares its start with the next one, so it is never the last such)
-        int lo = 0, hi = kScanTile - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (f_c0[mid] <= c) lo = mid; else hi = mid - 1;
-        }
-        const int t = lo;
+        const int t = last_at_most(f_c0, 0, kScanTile - 1, c);
         const int64_t j = c - f_c0[t];
         const int32_t du = f_du[t], di = f_di[t], nq = f_nq[t];
         const int64_t cu = (du + clen - 1) / clen;
@@ -499,11 +494,7 @@ __global__ void k_item_fill(const int64_t* __restrict__ wstart, const int64_t* _
   const int64_t total = wstart[nE];
   for (int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; w < total;
        w += (int64_t)gridDim.x * blockDim.x) {
-    int64_t lo = 0, hi = nE - 1;     // last entity t with wstart[t] <= w
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) >> 1;
-      if (wstart[mid] <= w) lo = mid; else hi = mid - 1;
-    }
+    const int64_t lo = last_at_most(wstart, (int64_t)0, nE - 1, w);     // last entity t with wstart[t] <= w
     const int64_t b = wstart[lo];
     const int64_t nqb = (gstart[lo + 1] - gstart[lo] + qb - 1) / qb;     // the entity's query count
     witems[3 * w] = (int32_t)lo;

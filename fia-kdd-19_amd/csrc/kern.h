@@ -1,6 +1,6 @@
-// Device-side definitions shared by the small-k FIA translation units (models.hip,
-// score_mf.hip): model traits, top-K order helpers, wave-level reductions, and the
-// per-batch kernel arguments.  gfx950 only.
+// Definitions shared by every translation unit but index.hip, bigk.hip and abi.hip: the model
+// traits and the dispatch from (model, k) to them, top-K order helpers and selections,
+// wave-level reductions, and the per-batch kernel arguments.  gfx950 only.
 #pragma once
 
 #include <cmath>
@@ -47,6 +47,17 @@ struct NCFm {
   }
 };
 
+// f(M{}) with M the traits of (model, k): the small sizes; every size (the kernels that read only
+// the parameter tables are built for the large k too).  False, f not called: not such a size.
+template <class F>
+bool dispatch_small(int model, int k, F&& f) {
+  return for_small_size<MFm, NCFm>(model, k, f);
+}
+template <class F>
+bool dispatch_any(int model, int k, F&& f) {
+  return for_small_size<MFm, NCFm>(model, k, f) || for_big_size<MFm, NCFm>(model, k, f);
+}
+
 __device__ __forceinline__ int tri(int r, int c) { return (r * (r + 1)) / 2 + c; }
 
 // Gram cache element (R >= C) of one side block.  Packed lower triangle, except NCF k = 16
@@ -77,6 +88,12 @@ __device__ __forceinline__ double readlane_d(double v, int l) {
   const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
   const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
   return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+
+__device__ __forceinline__ double wave_sum(double x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
+  return x;
 }
 
 template <int N>
@@ -160,6 +177,22 @@ __device__ __forceinline__ void wave_best(double& a, int& p, double& v) {
   best_row_step<true>(a, p, v);
 }
 
+// The best (key, position, value) of a workgroup of NW waves, in every thread (s_*: NW entries)
+template <int NW>
+__device__ __forceinline__ void block_best(double& ba, int& bp, double& bv, double* s_a, int* s_p, double* s_v) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  wave_best(ba, bp, bv);
+  if (NW > 1) {
+    if (lane == 0) { s_a[wave] = ba; s_p[wave] = bp; s_v[wave] = bv; }
+    __syncthreads();
+    ba = s_a[0]; bp = s_p[0]; bv = s_v[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w)
+      if (better(s_a[w], s_p[w], ba, bp)) { ba = s_a[w]; bp = s_p[w]; bv = s_v[w]; }
+    __syncthreads();
+  }
+}
+
 // Block-wide K-round selection over per-thread candidate lists (NC each).  Round t
 // takes the best candidate strictly worse than round t-1's winner, so no
 // "taken" marks are needed (positions are unique).  Writes K (pos, val) pairs.
@@ -167,8 +200,6 @@ template <int NC, int NT>
 __device__ void block_topk(const double (&ca)[NC], const int (&cp)[NC], const double (&cv)[NC], int K,
                            int32_t* __restrict__ out_pos, double* __restrict__ out_val, double* s_a, int* s_p,
                            double* s_v) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr int NW = NT / 64;
   double pa = INFINITY;
   int pp = -1;
   for (int t = 0; t < K; ++t) {
@@ -180,16 +211,7 @@ __device__ void block_topk(const double (&ca)[NC], const int (&cp)[NC], const do
         ba = ca[c]; bp = cp[c]; bv = cv[c];
       }
     }
-    wave_best(ba, bp, bv);
-    if (NW > 1) {
-      if (lane == 0) { s_a[wave] = ba; s_p[wave] = bp; s_v[wave] = bv; }
-      __syncthreads();
-      ba = s_a[0]; bp = s_p[0]; bv = s_v[0];
-#pragma unroll
-      for (int w = 1; w < NW; ++w)
-        if (better(s_a[w], s_p[w], ba, bp)) { ba = s_a[w]; bp = s_p[w]; bv = s_v[w]; }
-      __syncthreads();
-    }
+    block_best<NT / 64>(ba, bp, bv, s_a, s_p, s_v);
     if (threadIdx.x == 0) {
       bool ok = ba > -1.5;
       out_pos[t] = ok ? bp : -1;
@@ -199,23 +221,15 @@ __device__ void block_topk(const double (&ca)[NC], const int (&cp)[NC], const do
   }
 }
 
-// One level of a batch-wide top-K merge (fia_total_influence, fia_self_influence): workgroup g
-// selects the K best of slots [g * FAN, (g + 1) * FAN) of `n_slots` (K entries each, position
-// -1 = none) into slot g of the next level, or, on the last level (one workgroup), into the
-// call's outputs.  Selection only: no value is changed on the way.
-template <int FAN>
-__global__ __launch_bounds__(256) void k_topk_merge(int64_t n_slots, int K, const int32_t* __restrict__ in_pos,
-                                                    const double* __restrict__ in_val,
-                                                    int32_t* __restrict__ out_pos, double* __restrict__ out_val,
-                                                    int64_t* __restrict__ topk_idx, double* __restrict__ topk_val) {
+// The same K rounds by a workgroup of 256 over `ncand` (position, value) candidates in memory
+// (position < 0 = none): thread 0 calls emit(t, ok, position, value) with round t's winner
+// (!ok: fewer than t + 1 candidates).  Selection only: no value is changed on the way.
+template <class Emit>
+__device__ __forceinline__ void block_topk_slots(int64_t ncand, const int32_t* __restrict__ cp,
+                                                 const double* __restrict__ cv, int K, Emit emit) {
   __shared__ double s_a[4], s_v[4];
   __shared__ int s_p[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t s0 = (int64_t)blockIdx.x * FAN;
-  const int64_t s1 = s0 + FAN < n_slots ? s0 + FAN : n_slots;
-  const int64_t ncand = (s1 > s0 ? s1 - s0 : 0) * K;
-  const int32_t* __restrict__ cp = in_pos + s0 * K;
-  const double* __restrict__ cv = in_val + s0 * K;
+  const int tid = threadIdx.x;
   double pa = INFINITY;
   int pp = -1;
   for (int t = 0; t < K; ++t) {
@@ -228,27 +242,34 @@ __global__ __launch_bounds__(256) void k_topk_merge(int64_t n_slots, int K, cons
       const double a = topk_key(val);
       if (better(pa, pp, a, p) && better(a, p, ba, bp)) { ba = a; bp = p; bv = val; }
     }
-    wave_best(ba, bp, bv);
-    if (lane == 0) { s_a[wave] = ba; s_p[wave] = bp; s_v[wave] = bv; }
-    __syncthreads();
-    ba = s_a[0]; bp = s_p[0]; bv = s_v[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w)
-      if (better(s_a[w], s_p[w], ba, bp)) { ba = s_a[w]; bp = s_p[w]; bv = s_v[w]; }
-    __syncthreads();
-    if (tid == 0) {
-      const bool ok = ba > -1.5;
-      if (topk_idx) {
-        topk_idx[t] = ok ? (int64_t)bp : -1;
-        topk_val[t] = ok ? bv : NAN;
-      } else {
-        out_pos[(int64_t)blockIdx.x * K + t] = ok ? bp : -1;
-        out_val[(int64_t)blockIdx.x * K + t] = ok ? bv : NAN;
-      }
-    }
+    block_best<4>(ba, bp, bv, s_a, s_p, s_v);
+    if (tid == 0) emit(t, ba > -1.5, bp, bv);
     pa = ba;
     pp = bp;
   }
+}
+
+// One level of a batch-wide top-K merge (fia_total_influence, fia_self_influence): workgroup g
+// selects the K best of slots [g * FAN, (g + 1) * FAN) of `n_slots` (K entries each, position
+// -1 = none) into slot g of the next level, or, on the last level (one workgroup), into the
+// call's outputs.
+template <int FAN>
+__global__ __launch_bounds__(256) void k_topk_merge(int64_t n_slots, int K, const int32_t* __restrict__ in_pos,
+                                                    const double* __restrict__ in_val,
+                                                    int32_t* __restrict__ out_pos, double* __restrict__ out_val,
+                                                    int64_t* __restrict__ topk_idx, double* __restrict__ topk_val) {
+  const int64_t s0 = (int64_t)blockIdx.x * FAN;
+  const int64_t s1 = s0 + FAN < n_slots ? s0 + FAN : n_slots;
+  const int64_t ncand = (s1 > s0 ? s1 - s0 : 0) * K;
+  block_topk_slots(ncand, in_pos + s0 * K, in_val + s0 * K, K, [&](int t, bool ok, int bp, double bv) {
+    if (topk_idx) {
+      topk_idx[t] = ok ? (int64_t)bp : -1;
+      topk_val[t] = ok ? bv : NAN;
+    } else {
+      out_pos[(int64_t)blockIdx.x * K + t] = ok ? bp : -1;
+      out_val[(int64_t)blockIdx.x * K + t] = ok ? bv : NAN;
+    }
+  });
 }
 
 // Slots (of K entries) that the levels of a merge of `first` slots need, the first level included:
@@ -324,5 +345,8 @@ struct QueryArgs {
   int64_t N;
   const double* d1tab;   // NCF k <= 16: d1 table [2^(k/2)][k] (k_ncf_d1_table)
 };
+// the context's index, caches and parameters as the small-k kernels read them (models.hip;
+// d1tab is set by the queries that read it)
+QueryArgs make_args(fia_ctx* c, const int32_t* qu, const int32_t* qi);
 
 }  // namespace fia

@@ -20,7 +20,7 @@
 #include <type_traits>
 
 #include "kern.h"
-#include "solve.h"   // ldlt_solve, wave_sum, solve_prologue, assemble_hessian
+#include "solve.h"   // ldlt_solve, solve_prologue, assemble_hessian
 
 namespace fia {
 namespace {
@@ -2483,33 +2483,21 @@ __global__ __launch_bounds__(256) void k_topk_merge_thread(
 // ------------------------------------------------------------------------------------
 // host-side dispatch
 // ------------------------------------------------------------------------------------
+}  // namespace
+
 QueryArgs make_args(fia_ctx* c, const int32_t* qu, const int32_t* qi) {
   QueryArgs A{};
+  fill_list_args(c, A);
   A.qu = qu;
   A.qi = qi;
-  A.U = c->p.U;
-  A.I = c->p.I;
-  for (int s = 0; s < 2; ++s) {
-    A.ptr[s] = c->idx.side[s].ptr.as<int64_t>();
-    A.row[s] = c->idx.side[s].row.as<int32_t>();
-    A.other[s] = c->idx.side[s].other.as<int32_t>();
-    A.rating[s] = c->idx.side[s].rating.as<float>();
-    A.gram[s] = c->gram[s].as<double>();
-    A.l1[s] = c->l1[s].as<double>();
-  }
-  for (int t = 0; t < 10; ++t) A.t[t] = c->p.t[t];
-  A.wd = c->p.wd;
-  A.damping = c->p.damping;
-  A.pairs.key = c->idx.pkey.as<unsigned long long>();
-  A.pairs.cnt = c->idx.pcnt.as<int32_t>();
-  A.pairs.sum = c->idx.psum.as<double>();
-  A.pairs.mask = (unsigned long long)(c->idx.pcap - 1);
   A.lgm[0] = c->gm[0].as<double>();
   A.lgm[1] = c->gm[1].as<double>();
   A.lres = c->resid.as<double>();
   A.N = c->idx.N;
   return A;
 }
+
+namespace {
 
 // MF k = 16: a quad of lanes per side system (k_solve_quad); MF k = 8: a thread per system
 template <class M>
@@ -2869,16 +2857,8 @@ topk:
 
 }  // namespace
 
-#define FIA_MODEL_CASES(X) \
-  X(FIA_MODEL_MF, 8, MFm<8>) X(FIA_MODEL_MF, 16, MFm<16>) X(FIA_MODEL_MF, 32, MFm<32>) \
-  X(FIA_MODEL_MF, 64, MFm<64>) X(FIA_MODEL_NCF, 8, NCFm<8>) X(FIA_MODEL_NCF, 16, NCFm<16>) \
-  X(FIA_MODEL_NCF, 32, NCFm<32>)
-
 bool model_supported(int model, int k) {
-#define X(m, kk, T) if (model == m && k == kk) return true;
-  FIA_MODEL_CASES(X)
-#undef X
-  return big_supported(model, k);
+  return dispatch_any(model, k, [](auto) {});
 }
 
 hipError_t launch_topk_merge(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, int K, int spc,
@@ -2912,9 +2892,8 @@ hipError_t prepare_model(fia_ctx* c, hipStream_t s, bool& unsupported) {
   unsupported = false;
   c->subset = false;
   c->small_subset = false;
-#define X(m, kk, T) if (c->p.model == m && c->p.k == kk) return prepare_impl<T>(c, s, nullptr);
-  FIA_MODEL_CASES(X)
-#undef X
+  hipError_t e = hipSuccess;
+  if (dispatch_small(c->p.model, c->p.k, [&](auto m) { e = prepare_impl<decltype(m)>(c, s, nullptr); })) return e;
   if (big_supported(c->p.model, c->p.k)) return prepare_big(c, 0, nullptr, nullptr, s);
   unsupported = true;
   return hipSuccess;
@@ -2961,16 +2940,11 @@ hipError_t prepare_model_for(fia_ctx* c, int64_t Q, const int32_t* qu, const int
     c->small_subset = false;
     return hipSuccess;
   }
-#define X(m, kk, T)                                                     \
-  if (c->p.model == m && c->p.k == kk) {                                \
-    FIA_HIP_TRY(prepare_impl<T>(c, ps, c->mark.as<uint8_t>()));         \
-    c->small_subset = true;                                             \
-    return hipSuccess;                                                  \
-  }
-  FIA_MODEL_CASES(X)
-#undef X
-  unsupported = true;
-  return hipSuccess;
+  hipError_t e = hipSuccess;
+  unsupported = !dispatch_small(c->p.model, c->p.k,
+                                [&](auto m) { e = prepare_impl<decltype(m)>(c, ps, c->mark.as<uint8_t>()); });
+  if (!unsupported && e == hipSuccess) c->small_subset = true;
+  return e;
 }
 
 hipError_t check_cover_small(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, int32_t* flag,
@@ -2987,12 +2961,12 @@ hipError_t query_model(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* 
                        int64_t* topk_pos, int64_t* topk_idx, double* topk_val, hipStream_t s, bool& unsupported,
                        const double* x_in) {
   unsupported = false;
-#define X(m, kk, T)                                                                                        \
-  if (c->p.model == m && c->p.k == kk)                                                                     \
-    return query_impl<T>(c, Q, qu, qi, offsets, max_chunks, rel_idx, influence, x_out, K, topk_pos, topk_idx, \
-                         topk_val, s, x_in);
-  FIA_MODEL_CASES(X)
-#undef X
+  hipError_t e = hipSuccess;
+  if (dispatch_small(c->p.model, c->p.k, [&](auto m) {
+        e = query_impl<decltype(m)>(c, Q, qu, qi, offsets, max_chunks, rel_idx, influence, x_out, K, topk_pos,
+                                    topk_idx, topk_val, s, x_in);
+      }))
+    return e;
   if (big_supported(c->p.model, c->p.k))
     return query_big(c, Q, qu, qi, offsets, max_chunks, rel_idx, influence, x_out, K, topk_pos, topk_idx, topk_val,
                      s, x_in);

@@ -33,7 +33,7 @@ namespace {
 
 constexpr int kCandRecGrid = 1 << 20; // most workgroups of the per-query kernels (grid-stride)
 
-struct CandArgs {
+struct CandArgs : ModelArgs {
   int64_t Q, total;
   const int32_t* qu;
   const int32_t* qi;
@@ -42,12 +42,7 @@ struct CandArgs {
   const int32_t* cu;
   const int32_t* ci;
   const float* cy;
-  int64_t U, I;
-  const int64_t* ptr[2];
-  const float* t[10];
-  const double* l1[2];
-  double wd;
-  int64_t tiles;          // ceil(total / kCandTile)
+  int64_t tiles;         // ceil(total / kCandTile)
   int32_t* tile_q;        // [tiles]: the query of each tile's first candidate (k_cand_rec)
 };
 
@@ -71,15 +66,6 @@ __global__ __launch_bounds__(64) void k_cand_rec(CandArgs A, double* __restrict_
     }
     query_record<M>(A, u, i, A.x + q * D, Rq, lane);
   }
-}
-
-// largest q in [lo, hi] with off[q] <= g (off[lo] <= g given)
-__device__ __forceinline__ int64_t cand_query(const int64_t* __restrict__ off, int64_t lo, int64_t hi, int64_t g) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
 }
 
 // MF: one dot for r-hat, one per matching side with x (d r-hat / d p_u = q_b, d r-hat / d q_i = p_a).
@@ -156,7 +142,7 @@ __global__ __launch_bounds__(kCandTile) void k_cand_score(CandArgs A, const doub
   float y = 0.f;
   bool valid = false;
   if (active) {
-    if (qhi != qlo) q = cand_query(A.off, qlo, qhi, g);
+    if (qhi != qlo) q = last_at_most(A.off, qlo, qhi, g);
     pos = (int)(g - A.off[q]);
     a = A.cu[g];
     b = A.ci[g];
@@ -217,9 +203,6 @@ __global__ __launch_bounds__(256) void k_cand_merge(int64_t Q, int64_t total, co
                                                     const int32_t* __restrict__ cand_pos,
                                                     const double* __restrict__ cand_val,
                                                     int64_t* __restrict__ topk_pos, double* __restrict__ topk_val) {
-  __shared__ double s_a[4], s_v[4];
-  __shared__ int s_p[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
     // (clamped to the scored range: offsets that break cand_offsets[Q] == total_cand still
     // read inside the reserved slots)
@@ -227,37 +210,10 @@ __global__ __launch_bounds__(256) void k_cand_merge(int64_t Q, int64_t total, co
     const int64_t b = off[q] < e ? (off[q] > 0 ? off[q] : 0) : e;
     const int64_t t0 = b / kCandTile;
     const int64_t nt = e > b ? (e - 1) / kCandTile - t0 + 1 : 0;
-    const int64_t ncand = nt * K;
-    const int32_t* __restrict__ cp = cand_pos + (t0 + q) * K;
-    const double* __restrict__ cv = cand_val + (t0 + q) * K;
-    double pa = INFINITY;
-    int pp = -1;
-    for (int t = 0; t < K; ++t) {
-      double ba = -2.0, bv = 0.0;
-      int bp = 0x7fffffff;
-      for (int64_t j = tid; j < ncand; j += 256) {
-        const int p = cp[j];
-        if (p < 0) continue;
-        const double val = cv[j];
-        const double a = topk_key(val);
-        if (better(pa, pp, a, p) && better(a, p, ba, bp)) { ba = a; bp = p; bv = val; }
-      }
-      wave_best(ba, bp, bv);
-      if (lane == 0) { s_a[wave] = ba; s_p[wave] = bp; s_v[wave] = bv; }
-      __syncthreads();
-      ba = s_a[0]; bp = s_p[0]; bv = s_v[0];
-#pragma unroll
-      for (int w = 1; w < 4; ++w)
-        if (better(s_a[w], s_p[w], ba, bp)) { ba = s_a[w]; bp = s_p[w]; bv = s_v[w]; }
-      __syncthreads();
-      if (tid == 0) {
-        const bool ok = ba > -1.5;
-        topk_pos[q * K + t] = ok ? (int64_t)bp : -1;
-        topk_val[q * K + t] = ok ? bv : NAN;
-      }
-      pa = ba;
-      pp = bp;
-    }
+    block_topk_slots(nt * K, cand_pos + (t0 + q) * K, cand_val + (t0 + q) * K, K, [&](int t, bool ok, int bp, double bv) {
+      topk_pos[q * K + t] = ok ? (int64_t)bp : -1;
+      topk_val[q * K + t] = ok ? bv : NAN;
+    });
   }
 }
 
@@ -304,8 +260,9 @@ hipError_t score_impl(fia_ctx* c, const CandArgs& A0, double* influence, int K, 
 hipError_t score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const double* x,
                             const int64_t* cand_offsets, int64_t total_cand, const int32_t* cand_user,
                             const int32_t* cand_item, const float* cand_rating, double* influence, int K,
-                            int64_t* topk_pos, double* topk_val, hipStream_t s, bool& unsupported) {
+                            int64_t* topk_pos, double* topk_val, hipStream_t s) {
   CandArgs A{};
+  fill_model_args(c, A);
   A.Q = Q;
   A.total = total_cand;
   A.qu = qu;
@@ -315,32 +272,10 @@ hipError_t score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int3
   A.cu = cand_user;
   A.ci = cand_item;
   A.cy = cand_rating;
-  A.U = c->p.U;
-  A.I = c->p.I;
-  for (int sd = 0; sd < 2; ++sd) {
-    A.ptr[sd] = c->idx.side[sd].ptr.as<int64_t>();
-    A.l1[sd] = c->l1[sd].as<double>();
-  }
-  for (int t = 0; t < 10; ++t) A.t[t] = c->p.t[t];
-  A.wd = c->p.wd;
-  unsupported = false;
-#define FIA_CAND_CASE(MODEL, KV, T)                                              \
-  if (c->p.model == MODEL && c->p.k == KV) return score_impl<T<KV>>(c, A, influence, K, topk_pos, topk_val, s);
-  FIA_CAND_CASE(FIA_MODEL_MF, 8, MFm)
-  FIA_CAND_CASE(FIA_MODEL_MF, 16, MFm)
-  FIA_CAND_CASE(FIA_MODEL_MF, 32, MFm)
-  FIA_CAND_CASE(FIA_MODEL_MF, 64, MFm)
-  FIA_CAND_CASE(FIA_MODEL_MF, 128, MFm)
-  FIA_CAND_CASE(FIA_MODEL_MF, 256, MFm)
-  FIA_CAND_CASE(FIA_MODEL_NCF, 8, NCFm)
-  FIA_CAND_CASE(FIA_MODEL_NCF, 16, NCFm)
-  FIA_CAND_CASE(FIA_MODEL_NCF, 32, NCFm)
-  FIA_CAND_CASE(FIA_MODEL_NCF, 64, NCFm)
-  FIA_CAND_CASE(FIA_MODEL_NCF, 128, NCFm)
-  FIA_CAND_CASE(FIA_MODEL_NCF, 256, NCFm)
-#undef FIA_CAND_CASE
-  unsupported = true;
-  return hipSuccess;
+  hipError_t e = hipErrorInvalidValue;      // (model_supported is checked by the caller)
+  dispatch_any(c->p.model, c->p.k,
+               [&](auto m) { e = score_impl<decltype(m)>(c, A, influence, K, topk_pos, topk_val, s); });
+  return e;
 }
 
 }  // namespace fia

@@ -65,7 +65,7 @@ constexpr int64_t self_lds_bytes() {
 
 template <class M, bool COPY>
 __global__ __launch_bounds__(kSolveThreads) void k_self(QueryArgs A, SelfArgs S) {
-  constexpr int K = M::K, Ds = M::Ds, D = M::D, T = D * (D + 1) / 2;
+  constexpr int K = M::K, D = M::D, T = D * (D + 1) / 2;
   __shared__ double H[T];
   __shared__ double H2[COPY ? T : 1];
   __shared__ double g[D], th[D], dd[D], ww[D];
@@ -96,11 +96,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_self(QueryArgs A, SelfArgs S)
     if (lane == 0 && S.error) S.error[p] = e;
     if (!want_first && !want_newton) continue;
     const double mn = 2.0 / (double)n;                // m_j / n
-    const double s2 = 2.0 * mn;
-    for (int c = lane; c < D; c += kSolveThreads) {
-      const double dec = M::decayed(c < Ds ? c : c - Ds) ? A.wd : 0.0;
-      bj[c] = mn * (2.0 * e * g[c] + dec * th[c]);
-    }
+    for (int c = lane; c < D; c += kSolveThreads) bj[c] = member_rhs<M>(c, g, th, e, mn, A.wd);
     // two passes through one solve: 0 = H x = v and the dot with b_j; 1 = H again, downdated,
     // solved for b_j in place, and the dot with v
 #pragma nounroll
@@ -121,22 +117,8 @@ __global__ __launch_bounds__(kSolveThreads) void k_self(QueryArgs A, SelfArgs S)
         __syncthreads();
       }
       if (down) {
-        // H - H_j: the three terms k_group takes out for a member on both sides (g_j = v, m_j = 2)
-#pragma nounroll
-        for (int r = 0; r < D; ++r) {
-          const double gr = s2 * g[r];
-          double* __restrict__ Hr = Hs + tri(r, 0);
-          for (int c = lane; c <= r; c += kSolveThreads) Hr[c] = fma(-gr, g[c], Hr[c]);
-        }
-        __syncthreads();                              // (NCF: the coupling entries are other lanes' above)
-        for (int c = lane; c < K; c += kSolveThreads) {
-          if constexpr (!M::ncf) Hs[tri(Ds + c, c)] -= s2 * e;                          // I on (p_u, q_i)
-          else Hs[tri(Ds + K + c, K + c)] -= s2 * e * w.W3[K / 2 + c];                  // diag(W3g) on (Pg_u, Qg_i)
-        }
-        for (int c = lane; c < D; c += kSolveThreads) {
-          const double dec = M::decayed(c < Ds ? c : c - Ds) ? A.wd : 0.0;
-          Hs[tri(c, c)] -= mn * dec;
-        }
+        // H - H_j: a member on both sides (g_j = v, m_j = 2)
+        remove_member<M>(Hs, g, e, mn, 0, D, true, w, A.wd);
         __syncthreads();
       }
       double* rhs = down ? bj : x;
@@ -205,8 +187,7 @@ hipError_t self_influence(fia_ctx* c, int64_t n, const int32_t* rows, double* fi
         newton = c->gxq.as<double>();
       }
     }
-    QueryArgs A{};
-    solve_query_args(c, A);
+    const QueryArgs A = make_args(c, nullptr, nullptr);
     SelfArgs S{};
     S.n = n;
     S.rows = rows;
@@ -214,16 +195,7 @@ hipError_t self_influence(fia_ctx* c, int64_t n, const int32_t* rows, double* fi
     S.newton = newton;
     S.error = error;
     hipError_t e = hipErrorInvalidValue;              // (group_supported is checked by the caller)
-#define FIA_SELF_CASE(MODEL, KV, T) \
-  if (c->p.model == MODEL && c->p.k == KV) e = self_impl<T<KV>>(c, A, S, s);
-    FIA_SELF_CASE(FIA_MODEL_MF, 8, MFm)
-    FIA_SELF_CASE(FIA_MODEL_MF, 16, MFm)
-    FIA_SELF_CASE(FIA_MODEL_MF, 32, MFm)
-    FIA_SELF_CASE(FIA_MODEL_MF, 64, MFm)
-    FIA_SELF_CASE(FIA_MODEL_NCF, 8, NCFm)
-    FIA_SELF_CASE(FIA_MODEL_NCF, 16, NCFm)
-    FIA_SELF_CASE(FIA_MODEL_NCF, 32, NCFm)
-#undef FIA_SELF_CASE
+    dispatch_small(c->p.model, c->p.k, [&](auto m) { e = self_impl<decltype(m)>(c, A, S, s); });
     FIA_HIP_TRY(e);
   }
   if (K <= 0) return hipSuccess;

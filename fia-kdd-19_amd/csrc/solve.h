@@ -1,9 +1,9 @@
 // Device code of the full-D per-query system, shared by models.hip (k_solve, k_record_x and
 // the side-system solves' prologue), group.hip (fia_group_influence) and self.hip
 // (fia_self_influence): the LDS LDL^T, the
-// query prologue (theta_t, v = d r-hat / d theta_t, r-hat of one pair) and the assembly of the
-// packed coupled Hessian from the two entity Gram caches.  One wave (kSolveThreads) per system
-// unless a function says otherwise.
+// query prologue (theta_t, v = d r-hat / d theta_t, r-hat of one pair), the assembly of the
+// packed coupled Hessian from the two entity Gram caches and the removal of one train row from
+// it.  One wave (kSolveThreads) per system unless a function says otherwise.
 #pragma once
 
 #include "kern.h"
@@ -41,12 +41,6 @@ __device__ void ldlt_solve(double* H, double* v, double* d, double* w, int lo, i
     for (int c = lo + lane; c < j; c += kSolveThreads) v[c] = fma(-Lj[c], xj, v[c]);
     __syncthreads();
   }
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  return x;
 }
 
 
@@ -174,6 +168,49 @@ __device__ __forceinline__ bool assemble_hessian(const QueryArgs& A, int32_t u, 
   return coupled;
 }
 
+// Removing train row j = (a, b, y) from the system of a query it is related to (group.hip's
+// header): g_j = d r-hat(a, b) / d theta_t with the blocks of a side that does not match the
+// query zeroed, e = r-hat(a, b) - y, mn = m_j / n.
+//
+// H -= the member's three terms on the packed triangle: (2 m_j / n) g_j g_j^T over rows and
+// columns [r0, r1) (the blocks where g_j is nonzero); own -- the member is the query's own pair
+// -- (2 m_j / n) e_j C_j, the coupling of the user and item blocks; and (m_j / n) wd M.  One
+// wave; the caller synchronises before H is read.
+template <class M>
+__device__ __forceinline__ void remove_member(double* H, const double* gj, double e, double mn, int r0, int r1,
+                                              bool own, const NCFWeights<M::ncf ? M::K : 2>& w, double wd) {
+  constexpr int K = M::K, Ds = M::Ds, D = M::D;
+  const int lane = threadIdx.x;
+  const double s2 = 2.0 * mn;
+#pragma nounroll
+  for (int r = r0; r < r1; ++r) {
+    const double gr = s2 * gj[r];
+    double* __restrict__ Hr = H + tri(r, 0);
+    for (int c = r0 + lane; c <= r; c += kSolveThreads) Hr[c] = fma(-gr, gj[c], Hr[c]);
+  }
+  // the entries below were other lanes' above: NCF's coupling entry (Ds + K + c, K + c) lane
+  // (K + c) % 64's, a diagonal entry (c, c) lane (c - r0) % 64's
+  __syncthreads();
+  if (own) {
+    for (int c = lane; c < K; c += kSolveThreads) {
+      if constexpr (!M::ncf) H[tri(Ds + c, c)] -= s2 * e;                         // I on (p_u, q_i)
+      else H[tri(Ds + K + c, K + c)] -= s2 * e * w.W3[K / 2 + c];                 // diag(W3g) on (Pg_u, Qg_i)
+    }
+  }
+  for (int c = lane; c < D; c += kSolveThreads) {
+    const double dec = M::decayed(c < Ds ? c : c - Ds) ? wd : 0.0;
+    H[tri(c, c)] -= mn * dec;
+  }
+}
+
+// ... and element c of its right-hand-side term (m_j / n) (2 e_j g_j + wd M theta_t)
+template <class M>
+__device__ __forceinline__ double member_rhs(int c, const double* gj, const double* th, double e, double mn,
+                                             double wd) {
+  const double dec = M::decayed(c < M::Ds ? c : c - M::Ds) ? wd : 0.0;
+  return mn * (2.0 * e * gj[c] + dec * th[c]);
+}
+
 // ids in range and related count of query (u, i); 0 for an id out of range (never an index)
 __device__ __forceinline__ int64_t related_count(const QueryArgs& A, int32_t u, int32_t i) {
   if (!(u >= 0 && u < A.U && i >= 0 && i < A.I)) return 0;
@@ -192,10 +229,9 @@ __device__ __forceinline__ void stage_ncf(const QueryArgs& A, NCFWeights<M::ncf 
   }
 }
 
-// ---- host side, shared by group.hip and self.hip (defined in group.hip) ----
-// the context's index, caches and parameters as the full-D kernels read them (qu / qi left null)
-void solve_query_args(const fia_ctx* c, QueryArgs& A);
-// c->rowrec: train row -> {user, item, rating bits, user-major list position}, built once per index
+// ---- host side, shared by group.hip and self.hip ----
+// c->rowrec: train row -> {user, item, rating bits, user-major list position}, built once per
+// index (group.hip)
 hipError_t ensure_rowrec(fia_ctx* c, hipStream_t s);
 // one-wave workgroups of `lds` bytes that the device keeps resident (160 KB of LDS per CU, at most
 // 16 per CU: 4 waves per SIMD at <= 128 VGPRs): the grid of a persistent full-D kernel

@@ -44,16 +44,12 @@ constexpr int kTotalFan = 16;           // slots merged by one workgroup of a to
                                         // (ml-1m, K = 64: fan 64 0.67 ms for the merge; see profiles/total_influence.md)
 constexpr int kTotalGrid = 1 << 20;     // most workgroups of the grid-stride kernels
 
-struct TotalArgs {
-  int64_t Q, N, U, I;
+struct TotalArgs : ModelArgs {
+  int64_t Q, N;
   const int32_t* qu;
   const int32_t* qi;
   const double* x;          // [Q * D], reference theta order
-  const int64_t* ptr[2];
-  const float* t[10];
-  const double* l1[2];
-  double wd;
-  const int32_t* row;       // user-major lists: train row, item, rating by list position
+  const int32_t* row;      // user-major lists: train row, item, rating by list position
   const int32_t* other;
   const float* rating;
   PairTable pairs;
@@ -155,15 +151,6 @@ __global__ __launch_bounds__(64) void k_total_agg(TotalArgs A) {
   }
 }
 
-// largest e in [lo, hi] with ptr[e] <= g (ptr[lo] <= g given): the owner of list position g
-__device__ __forceinline__ int64_t list_owner(const int64_t* __restrict__ ptr, int64_t lo, int64_t hi, int64_t g) {
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (ptr[mid] <= g) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // AGG: one thread per position of the user-major lists, scored against the two entities'
 // aggregates -> total / count / the tile's top-K.  !AGG: one thread per query, scored against
 // the query's own vectors at its own pair -> d_q (only where the pair is a train row).
@@ -192,14 +179,14 @@ __global__ __launch_bounds__(kTotalTile) void k_total_rows(TotalArgs A, double* 
   bool valid = false, on_u = false, on_i = false;
   if constexpr (AGG) {
     // the owners of the tile's first and last positions, then the thread's own between them
-    if (tid == 0) s_own[0] = list_owner(A.ptr[0], 0, A.U - 1, g0);
+    if (tid == 0) s_own[0] = last_at_most(A.ptr[0], (int64_t)0, A.U - 1, g0);
     if (tid == 64) {
       const int64_t last = g0 + kTotalTile < A.N ? g0 + kTotalTile - 1 : A.N - 1;
-      s_own[1] = list_owner(A.ptr[0], 0, A.U - 1, last);
+      s_own[1] = last_at_most(A.ptr[0], (int64_t)0, A.U - 1, last);
     }
     __syncthreads();
     if (active) {
-      a = (int32_t)list_owner(A.ptr[0], s_own[0], s_own[1], g);
+      a = (int32_t)last_at_most(A.ptr[0], s_own[0], s_own[1], g);
       b = A.other[g];
       row = A.row[g];
       sa = A.slot[a];
@@ -385,46 +372,22 @@ hipError_t total_impl(fia_ctx* c, TotalArgs A, double* total, int32_t* count, in
 
 hipError_t total_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const double* x,
                            double* total, int32_t* count, int K, int64_t* topk_idx, double* topk_val,
-                           hipStream_t s, bool& unsupported) {
+                           hipStream_t s) {
   TotalArgs A{};
+  fill_model_args(c, A);
   A.Q = Q;
   A.N = c->idx.N;
-  A.U = c->p.U;
-  A.I = c->p.I;
   A.qu = qu;
   A.qi = qi;
   A.x = x;
-  for (int sd = 0; sd < 2; ++sd) {
-    A.ptr[sd] = c->idx.side[sd].ptr.as<int64_t>();
-    A.l1[sd] = c->l1[sd].as<double>();
-  }
-  for (int t = 0; t < 10; ++t) A.t[t] = c->p.t[t];
-  A.wd = c->p.wd;
   A.row = c->idx.side[0].row.as<int32_t>();
   A.other = c->idx.side[0].other.as<int32_t>();
   A.rating = c->idx.side[0].rating.as<float>();
-  A.pairs.key = c->idx.pkey.as<unsigned long long>();
-  A.pairs.cnt = c->idx.pcnt.as<int32_t>();
-  A.pairs.sum = c->idx.psum.as<double>();
-  A.pairs.mask = (unsigned long long)(c->idx.pcap - 1);
-  unsupported = false;
-#define FIA_TOTAL_CASE(MODEL, KV, T)                                              \
-  if (c->p.model == MODEL && c->p.k == KV) return total_impl<T<KV>>(c, A, total, count, K, topk_idx, topk_val, s);
-  FIA_TOTAL_CASE(FIA_MODEL_MF, 8, MFm)
-  FIA_TOTAL_CASE(FIA_MODEL_MF, 16, MFm)
-  FIA_TOTAL_CASE(FIA_MODEL_MF, 32, MFm)
-  FIA_TOTAL_CASE(FIA_MODEL_MF, 64, MFm)
-  FIA_TOTAL_CASE(FIA_MODEL_MF, 128, MFm)
-  FIA_TOTAL_CASE(FIA_MODEL_MF, 256, MFm)
-  FIA_TOTAL_CASE(FIA_MODEL_NCF, 8, NCFm)
-  FIA_TOTAL_CASE(FIA_MODEL_NCF, 16, NCFm)
-  FIA_TOTAL_CASE(FIA_MODEL_NCF, 32, NCFm)
-  FIA_TOTAL_CASE(FIA_MODEL_NCF, 64, NCFm)
-  FIA_TOTAL_CASE(FIA_MODEL_NCF, 128, NCFm)
-  FIA_TOTAL_CASE(FIA_MODEL_NCF, 256, NCFm)
-#undef FIA_TOTAL_CASE
-  unsupported = true;
-  return hipSuccess;
+  A.pairs = pair_table(c->idx);
+  hipError_t e = hipErrorInvalidValue;      // (model_supported is checked by the caller)
+  dispatch_any(c->p.model, c->p.k,
+               [&](auto m) { e = total_impl<decltype(m)>(c, A, total, count, K, topk_idx, topk_val, s); });
+  return e;
 }
 
 }  // namespace fia
