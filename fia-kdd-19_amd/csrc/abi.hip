@@ -45,6 +45,14 @@ PhaseSpan phase_span(fia_ctx* c, int phase) {
   return ps;
 }
 
+void phase_drop(fia_ctx* c, int phase, const PhaseSpan& ps) {
+  auto& v = c->events.ev[phase];
+  if (!ps.a || v.empty() || v.back().first != ps.a) return;
+  c->events.pool.push_back(v.back().first);
+  c->events.pool.push_back(v.back().second);
+  v.pop_back();
+}
+
 // The stream a small-k Gram pass runs on: the context's aux stream, made to wait for
 // everything queued on `s` so far; `s` itself while `s` is being captured into a graph (a
 // fork there would have to be joined inside the same capture) or when aux is unavailable.

@@ -254,7 +254,11 @@ struct fia_ctx {
   fia::DevBuf qscan;      // k_query_scan tile words + counters (left zero by every launch)
   fia::DevBuf flag;       // int32 [4] device status words
   fia::DevBuf nch;        // int64 [Q+1] chunk counts
-  fia::DevBuf coupled;    // int32 [Q + 1]: count, then queries whose test pair is a train row
+  // int32 [Q + 2] {readers, count, q ...}: the queries whose test pair is a train row, appended by
+  // the side-system solve and finished by k_solve.  Zero when (re)allocated; k_solve takes the
+  // count and counts itself a reader with one 64-bit atomic on the first two words, and its last
+  // reader zeroes both, so every call finds the count zero without a memset or a launch
+  fia::DevBuf coupled;
   // query groups per entity (entity-shared scoring): global entity index g = e (users) or
   // U + e (items)
   fia::DevBuf gcnt;       // uint64 [U + I + 1] queries per entity -> exclusive scan in gstart
@@ -314,9 +318,6 @@ struct fia_ctx {
   bool l1_pending = false;
   unsigned profiling = 0;   // bit p: record phase p (fia_set_profiling)
   fia::PhaseEvents events;
-  // the chunk-list scan's timing events when that phase is its one kernel (stamped by its
-  // dispatch, no marker packets: query_impl sets them around build_chunks)
-  hipEvent_t scan_ev[2] = {nullptr, nullptr};
 };
 
 namespace fia {
@@ -498,7 +499,10 @@ hipError_t self_influence(fia_ctx* c, int64_t n, const int32_t* rows, double* fi
 // phase event helpers (no-ops unless profiling)
 void phase_begin(fia_ctx* c, int phase, hipStream_t s);
 void phase_end(fia_ctx* c, int phase, hipStream_t s);
+// (taken once the launch it times is known to proceed; phase_drop returns the pair of a launch
+// that failed after all, so no unrecorded pair is left for fia_profile_read)
 PhaseSpan phase_span(fia_ctx* c, int phase);
+void phase_drop(fia_ctx* c, int phase, const PhaseSpan& ps);
 
 }  // namespace fia
 

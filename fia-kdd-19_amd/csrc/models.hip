@@ -20,6 +20,7 @@
 #include <type_traits>
 
 #include "kern.h"
+#include "scan.h"    // query_scan_body: the scan role of k_solve_quad
 #include "solve.h"   // ldlt_solve, solve_prologue, assemble_hessian
 
 namespace fia {
@@ -104,11 +105,25 @@ __device__ void solve_epilogue(const QueryArgs& A, int64_t q, int32_t u, int32_t
 
 // One wave per query, the full D x D packed LDL^T: the queries whose test pair is a train row
 // (its Hessian couples the user and item blocks; the side-system solves list them in qlist
-// {count, q_0, q_1, ...}).
+// {count, q_0, q_1, ...}).  The word before the count counts this kernel's workgroups as they
+// read it: one 64-bit atomic on {readers, count} returns the count and the number of earlier
+// readers, and the last reader zeroes both words -- the list is empty again for the next call's
+// side-system solve, with no memset and no launch (and the same under a replayed graph).
 template <class M>
 __global__ __launch_bounds__(kSolveThreads, (M::Ds <= 33 ? 2 : 1)) void k_solve(QueryArgs A, int64_t Q, double* __restrict__ rec,
-                                                         double* __restrict__ x_out, const int32_t* __restrict__ qlist) {
+                                                         double* __restrict__ x_out, int32_t* __restrict__ qlist) {
   constexpr int K = M::K, Ds = M::Ds, D = M::D;
+  static_assert(kSolveThreads == 64, "one wave: lane 0's atomic is broadcast by a shuffle");
+  unsigned long long rw = 0;
+  {
+    unsigned long long* word = reinterpret_cast<unsigned long long*>(qlist - 1);
+    if (threadIdx.x == 0) {
+      rw = atomicAdd(word, 1ull);
+      if ((unsigned)(rw & 0xffffffffull) == gridDim.x - 1)
+        __hip_atomic_store(word, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    rw = __shfl(rw, 0);
+  }
   __shared__ double H[D * (D + 1) / 2];
   __shared__ double v[D], g[D], th[D], dd[D], ww[D];
   __shared__ double sh[4 * K + 8];
@@ -121,7 +136,7 @@ __global__ __launch_bounds__(kSolveThreads, (M::Ds <= 33 ? 2 : 1)) void k_solve(
     for (int t = threadIdx.x; t < 2 * K * K; t += blockDim.x) sW1[t] = (double)A.t[4][t];
     for (int t = threadIdx.x; t < K; t += blockDim.x) sb1[t] = (double)A.t[5][t];
   }
-  const int64_t nwork = qlist[0];
+  const int64_t nwork = (int64_t)(rw >> 32);
   for (int64_t wk = blockIdx.x; wk < nwork; wk += gridDim.x) {
   __syncthreads();
   const int64_t q = qlist[1 + wk];
@@ -1219,13 +1234,16 @@ __device__ __forceinline__ void quad_back(Quad16& Z, const double (&z)[4], doubl
   }
 }
 
+// one wave: the 8 queries [8 wv, 8 wv + 8) -- no LDS, no barrier, nothing read that another wave
+// of the launch writes
 template <class M>
-__global__ __launch_bounds__(64) void k_solve_quad(QueryArgs A, int64_t Q, double* __restrict__ rec,
-                                                   double* __restrict__ x_out, int32_t* __restrict__ coupled) {
+__device__ __forceinline__ void solve_quad_wave(const QueryArgs& A, int64_t Q, double* __restrict__ rec,
+                                                double* __restrict__ x_out, int32_t* __restrict__ coupled,
+                                                int64_t wv) {
   static_assert(!M::ncf && M::K == 16, "MF k = 16");
   constexpr int K = M::K, Ds = M::Ds, D = M::D, GS = Ds * (Ds + 1) / 2, GSP = (GS + 1) & ~1;
-  const int lane = threadIdx.x, qd = lane >> 2, j = lane & 3, h = qd >> 1, sd = qd & 1;
-  const int64_t q = (int64_t)blockIdx.x * 8 + h;
+  const int lane = threadIdx.x & 63, qd = lane >> 2, j = lane & 3, h = qd >> 1, sd = qd & 1;
+  const int64_t q = wv * 8 + h;
   const bool active = q < Q;
   const int64_t qc = active ? q : Q - 1;
   int32_t u = A.qu[qc], i = A.qi[qc];
@@ -1332,6 +1350,32 @@ __global__ __launch_bounds__(64) void k_solve_quad(QueryArgs A, int64_t Q, doubl
     for (int s = 0; s < 4; ++s) x_out[q * D + M::ref_index(sd * Ds + 4 * s + j)] = Z.x[s];
     if (j == 0) x_out[q * D + M::ref_index(sd * Ds + K)] = x16;
   }
+}
+
+// The chunk scan and the side-system solves of one batch in one launch: neither reads what the
+// other writes, both are latency-bound and each alone leaves most of the chip empty (ml-1m-ex:
+// 24 scan tiles; ~1.5 solve waves per SIMD), so one after the other they cost the sum of two
+// latency chains.  Workgroups [0, scan_tiles(Q)) run one tile of k_query_scan<1>'s body each,
+// the others eight waves of the quad solve (8 queries per wave, 64 per workgroup).  The register
+// budget is the larger role's: the solve's, two waves per SIMD, so a 512-thread workgroup is
+// one CU's worth and the static LDS is the scan's.
+// No workgroup waits on a workgroup that may not be running: a solve-role workgroup waits on
+// nothing any other workgroup writes; a scan-role workgroup waits only on the tile words of
+// EARLIER tickets, and a ticket is drawn by a workgroup that has already started -- so whatever
+// order the dispatcher starts the roles in, every awaited workgroup is resident and runs to its
+// publish without waiting on a later one.  The `coupled` count the solve role appends to is not
+// touched by the scan role (the scan's zero_word is null here): k_solve leaves it zero.
+template <class M>
+__global__ __launch_bounds__(kScanThreads) void k_solve_quad(ScanArgs S, QueryArgs A, double* __restrict__ rec,
+                                                             double* __restrict__ x_out,
+                                                             int32_t* __restrict__ coupled) {
+  const unsigned ntiles = (unsigned)((S.Q + 1 + kScanTile - 1) / kScanTile);
+  if (blockIdx.x < ntiles) {
+    query_scan_body<1>(S);
+    return;
+  }
+  solve_quad_wave<M>(A, S.Q, rec, x_out, coupled,
+                     (int64_t)(blockIdx.x - ntiles) * (kScanThreads / 64) + (threadIdx.x >> 6));
 }
 
 // ------------------------------------------------------------------------------------
@@ -2699,31 +2743,38 @@ hipError_t query_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
   // every (entity chunk, query block) item covers >= 1 per-query chunk
   const int64_t max_items = max_chunks;
   // the queries whose test pair is a train row are listed in `coupled` {count, q...} by the
-  // solve and finished full-D; the chunk scan zeroes the count
-  FIA_HIP_TRY(c->coupled.reserve(sizeof(int32_t) * (size_t)(Q + 1), s));
-  // MF k <= 16: the chunk phase is the one scan kernel and the solve phase the side-system solve
-  // + the coupled solve, so their events are stamped by those kernels' dispatches (a marker
-  // packet per event idled the GPU ~5 us: RQ2's single query)
-  constexpr bool ext_phases = runs && !M::ncf && use_quad_solve<M>();
-  PhaseSpan cspan;
-  if (ext_phases) {
-    cspan = phase_span(c, 4);
-    c->scan_ev[0] = cspan.a;
-    c->scan_ev[1] = cspan.b;
-  } else {
-    phase_begin(c, 4, s);
+  // solve and finished full-D by k_solve, whose last reader leaves {readers, count} zero (the
+  // word pair in front of the list: fia_ctx::coupled); zero when (re)allocated
+  if (c->coupled.bytes < sizeof(int32_t) * (size_t)(Q + 2) || !c->coupled.ptr) {
+    FIA_HIP_TRY(c->coupled.reserve(sizeof(int32_t) * (size_t)(Q + 2), s));
+    FIA_HIP_TRY(hipMemsetAsync(c->coupled.ptr, 0, c->coupled.bytes, s));
   }
+  int32_t* const coupled = c->coupled.as<int32_t>() + 1;
+  // MF k = 16: the chunk scan and the side-system solves are one launch (k_solve_quad), timed
+  // with the coupled solve as the solve phase -- the chunk phase then records nothing.  Without
+  // a solve (a given x, an empty batch) the chunk phase is the one scan kernel.  Either way the
+  // events are stamped by those kernels' dispatches (a marker packet per event idled the GPU
+  // ~5 us: RQ2's single query), and a pair is taken only once its launch is known to proceed.
+  constexpr bool ext_phases = runs && !M::ncf && use_quad_solve<M>();
+  const bool fused = ext_phases && Q > 0 && !x_in;
+  if (!ext_phases) phase_begin(c, 4, s);
   // MF k <= 16 item runs: one wave per equal-cost slice of the descriptor list (descriptor
   // costs vary ~10x: a static stride over descriptors left waves idle for half the kernel);
   // the slice count is known on the device only -- the grid is its bound (total cost <=
   // kRunUserCost per descriptor slot), the surplus waves exit at once
   constexpr int64_t lam = kRunLambda;
   const int64_t runs_grid = (kRunUserCost * (max_chunks + 1)) / lam + 2;
-  {
-    const hipError_t eb = build_chunks(c, Q, qu, qi, offsets, max_chunks, grouped, s, c->coupled.as<int32_t>(), runs,
-                                       (int)lam, M::ncf ? kNcfRunChunk : kRunChunk);
-    c->scan_ev[0] = c->scan_ev[1] = nullptr;
-    FIA_HIP_TRY(eb);
+  // (the fused launch's solve role appends to the count while its scan role runs: the scan
+  // zeroes it only where it is a launch of its own, ahead of the solve)
+  ScanArgs S;
+  FIA_HIP_TRY(chunk_scan_args(c, Q, qu, qi, offsets, max_chunks, grouped, s, fused ? nullptr : coupled, runs, (int)lam,
+                              M::ncf ? kNcfRunChunk : kRunChunk, S));
+  if (!fused) {
+    const PhaseSpan cspan = ext_phases ? phase_span(c, 4) : PhaseSpan{};
+    if (const hipError_t eb = launch_chunk_scan(S, s, cspan.a, cspan.b); eb != hipSuccess) {
+      phase_drop(c, 4, cspan);
+      return eb;
+    }
   }
   if (grouped) FIA_HIP_TRY(build_groups(c, Q, qu, qi, offsets, max_items, qblock, s, use_mfma ? kMfmaCPI : 1));
   // the query-side work that needs no Gram cache, ahead of the join with a pending prepare:
@@ -2750,10 +2801,9 @@ hipError_t query_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
   }
   if (!ext_phases) phase_end(c, 4, s);
   FIA_HIP_TRY(join_prepare(c, s));     // the Gram caches (and NCF rows) of a pending fia_prepare
-  const bool ext_solve = ext_phases && Q > 0 && !x_in;
+  const bool ext_solve = fused;
   PhaseSpan sspan;
-  if (ext_solve) sspan = phase_span(c, 1);
-  else phase_begin(c, 1, s);
+  if (!ext_solve) phase_begin(c, 1, s);
   if (x_in && Q > 0) {
     // a given inverse HVP: records straight from it, no solve (fia_query_batch_x)
     const int64_t g1 = Q < 8192 ? Q : 8192;
@@ -2764,28 +2814,34 @@ hipError_t query_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
   // non-coupled queries: thread-per-system (MF k <= 16) or column-parallel blocks
   if (Q > 0 && !x_in) {
     if constexpr (use_quad_solve<M>()) {
-      hipExtLaunchKernelGGL(k_solve_quad<M>, dim3((unsigned)((Q + 7) / 8)), dim3(64), 0, s, sspan.a, (hipEvent_t) nullptr, 0, A, Q,
-                            c->rec.as<double>(), x_out, c->coupled.as<int32_t>());
+      // scan_tiles(Q) scan workgroups, then 64 queries per solve workgroup; the solve phase's
+      // start is this dispatch, its end k_solve's
+      sspan = phase_span(c, 1);
+      hipExtLaunchKernelGGL(k_solve_quad<M>, dim3((unsigned)(scan_tiles(Q) + (Q + 63) / 64)), dim3(kScanThreads), 0, s,
+                            sspan.a, (hipEvent_t) nullptr, 0, S, A, c->rec.as<double>(), x_out, coupled);
     } else if constexpr (use_tps<M>()) {
       hipLaunchKernelGGL(k_solve_tps<M>, dim3((unsigned)((2 * Q + 63) / 64)), dim3(64), 0, s, A, Q,
-                         c->rec.as<double>(), x_out, c->coupled.as<int32_t>());
+                         c->rec.as<double>(), x_out, coupled);
     } else if constexpr (pair_layout<M>()) {
       hipLaunchKernelGGL(k_solve_rows<M>, dim3((unsigned)((Q + 1) / 2)), dim3(64), 0, s, A, Q,
-                         (const double*)c->qwork.as<double>(), c->rec.as<double>(), x_out, c->coupled.as<int32_t>());
+                         (const double*)c->qwork.as<double>(), c->rec.as<double>(), x_out, coupled);
     } else if constexpr (use_col_solve<M>()) {
       const int64_t cap = (int64_t)(c->num_cus > 0 ? c->num_cus : 256) * 16;
       constexpr int QW = 32 / M::K;             // queries per wave
       const int64_t need = (Q + QW - 1) / QW;
       const int64_t g1 = need < cap ? need : cap;   // persistent: NCF weights staged once per block
       hipLaunchKernelGGL(k_solve_col<M>, dim3((unsigned)g1), dim3(64), 0, s, A, Q, c->rec.as<double>(), x_out,
-                         c->coupled.as<int32_t>());
+                         coupled);
     } else {
       const int64_t cap = (int64_t)(c->num_cus > 0 ? c->num_cus : 256) * 8;
       const int64_t g1 = Q < cap ? Q : cap;     // persistent: NCF weights staged once per block
       hipLaunchKernelGGL(k_solve_tile<M>, dim3((unsigned)g1), dim3(128), 0, s, A, Q, c->rec.as<double>(), x_out,
-                         c->coupled.as<int32_t>());
+                         coupled);
     }
-    FIA_HIP_TRY(hipGetLastError());
+    if (const hipError_t es = hipGetLastError(); es != hipSuccess) {
+      phase_drop(c, 1, sspan);
+      return es;
+    }
     // usually no coupled query: a small grid that exits (a full grid for the large full-D
     // systems of k >= 32, should many test pairs be train rows).  (Folding this into the last
     // workgroup of k_solve_tps -- an atomic finish count -- made that kernel 14 us slower at
@@ -2793,7 +2849,11 @@ hipError_t query_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
     const int64_t gc = M::K <= 16 ? 64 : 256;
     const int64_t g2 = Q < gc ? Q : gc;
     hipExtLaunchKernelGGL(k_solve<M>, dim3((unsigned)g2), dim3(kSolveThreads), 0, s, (hipEvent_t) nullptr,
-                          sspan.b, 0, A, Q, c->rec.as<double>(), x_out, (const int32_t*)c->coupled.as<int32_t>());
+                          sspan.b, 0, A, Q, c->rec.as<double>(), x_out, coupled);
+    if (const hipError_t es = hipGetLastError(); es != hipSuccess) {
+      phase_drop(c, 1, sspan);
+      return es;
+    }
   }
   if constexpr (mask_path<M>()) {
     if (Q > 0) {       // the records' MLP block -> y = W1_side^T x_mlp for k_score_ncf

@@ -392,7 +392,14 @@ int fia_num_params(const fia_ctx* ctx);
  * them, returns per-phase sums (ms) and counts, and clears them.
  * Phases: 0 prepare, 1 solve, 2 score (the dominant gather/scoring kernel),
  * 3 topk merge, 4 chunk build + scan.  Each pair costs a little stream time,
- * so timed runs enable only the phase they price. */
+ * so timed runs enable only the phase they price.
+ * MF k = 16, fia_query_batch: the chunk scan runs inside the side-system solve's
+ * launch, so phase 1 (solve) spans that launch and the coupled solve -- chunk
+ * scan included -- and phase 4 records nothing (count 0) for such a call; the sum
+ * of phases 4 and 1 means what it meant.  fia_query_batch_x has no solve: there
+ * phase 4 is the scan as before.  These pairs are taken right before the launch
+ * that stamps them and returned if it fails, so a failed call leaves no
+ * unrecorded pair for fia_profile_read. */
 #define FIA_NUM_PHASES 5
 #define FIA_PROFILE_ALL 0x1f
 int fia_set_profiling(fia_ctx* ctx, int phase_mask);
