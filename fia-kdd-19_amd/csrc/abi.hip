@@ -256,7 +256,8 @@ int fia_destroy(fia_ctx* c) {
                            &c->gcnt,   &c->gstart, &c->grank,    &c->gq,        &c->qbase,    &c->gscan,
                            &c->wstart, &c->witems, &c->resid,  &c->qwork,  &c->xb,       &c->syslist,
                            &c->cpllist, &c->lscr, &c->mark, &c->d1tab, &c->slices, &c->wfrag,
-                           &c->tkeys, &c->tvals, &c->tagg, &c->tslot, &c->tword, &c->tsort, &c->rowrec, &c->gxq};
+                           &c->tkeys, &c->tvals, &c->tagg, &c->tslot, &c->tword, &c->tsort, &c->rowrec, &c->gxq,
+                           &c->dwork, &c->dslab, &c->dpairs};
     for (auto* b : bufs) rel(*b);
     if (can_free) (void)hipStreamSynchronize(ds);   // the stream-ordered frees complete
     if (c->aux && !capturing) (void)hipStreamDestroy(c->aux);
@@ -585,17 +586,24 @@ int fia_group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t*
     if (Q == 0 || num_groups == 0) return FIA_OK;
     if (!qu || !qi || !grp_offsets || !mem_offsets) return fail(c, FIA_ERR_INVALID, "null query or offset array");
     if (total_members > 0 && !mem_row) return fail(c, FIA_ERR_INVALID, "null member array");
-    if (!fia::group_supported(c->p.model, c->p.k))
+    // small k: the full packed system in LDS (group.hip); large k: in device memory (group_big.hip)
+    const bool big = fia::big_supported(c->p.model, c->p.k);
+    if (!big && !fia::group_supported(c->p.model, c->p.k))
       return fail(c, FIA_ERR_UNSUPPORTED,
-                  "fia_group_influence is built for MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32} (the full "
-                  "packed system in LDS); the large-k models keep their systems in device memory");
+                  "fia_group_influence is built for MF k in {8, 16, 32, 64, 128, 256} and NCF k in {8, 16, 32, 64, "
+                  "128, 256}");
     DeviceGuard g(c->device);
     hipStream_t s = as_stream(stream);
     if (int rc = enter_stream(c, s, "fia_group_influence"); rc != FIA_OK) return rc;
     // the Gram caches of a pending small-k pass are read: join it, as fia_query_batch's solve does
     if (hipError_t es = fia::join_prepare(c, s); es != hipSuccess) return hip_fail(c, es, "fia_group_influence");
-    hipError_t e = fia::group_influence(c, Q, qu, qi, grp_offsets, num_groups, mem_offsets, total_members, mem_row,
-                                        group, first_order, dtheta, s);
+    // (large k after fia_prepare_for: a query outside the cover gets n = 0 from the prologue, as in
+    // fia_query_batch, and its groups NaN before any member is read; fia_count_related with a total
+    // is the call that refuses such a batch)
+    hipError_t e = big ? fia::group_influence_big(c, Q, qu, qi, grp_offsets, num_groups, mem_offsets, total_members,
+                                                  mem_row, group, first_order, dtheta, s)
+                       : fia::group_influence(c, Q, qu, qi, grp_offsets, num_groups, mem_offsets, total_members,
+                                              mem_row, group, first_order, dtheta, s);
     if (e != hipSuccess) return hip_fail(c, e, "fia_group_influence");
     return FIA_OK;
   })
@@ -628,10 +636,11 @@ int fia_self_influence(fia_ctx* c, int64_t num_rows, const int32_t* rows, double
     }
     if (!rows && num_rows != c->idx.N)
       return fail(c, FIA_ERR_INVALID, "rows is NULL (every train row): num_rows must equal n_train");
-    if (!fia::group_supported(c->p.model, c->p.k))
+    // (self_influence takes the large-k sizes to group_big.hip)
+    if (!fia::group_supported(c->p.model, c->p.k) && !fia::big_supported(c->p.model, c->p.k))
       return fail(c, FIA_ERR_UNSUPPORTED,
-                  "fia_self_influence is built for MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32} (the full "
-                  "packed system in LDS); the large-k models keep their systems in device memory");
+                  "fia_self_influence is built for MF k in {8, 16, 32, 64, 128, 256} and NCF k in {8, 16, 32, 64, "
+                  "128, 256}");
     if (int rc = enter_stream(c, s, "fia_self_influence"); rc != FIA_OK) return rc;
     // the Gram caches of a pending small-k pass are read: join it, as fia_group_influence does
     if (hipError_t es = fia::join_prepare(c, s); es != hipSuccess) return hip_fail(c, es, "fia_self_influence");

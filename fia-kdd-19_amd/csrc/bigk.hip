@@ -28,27 +28,13 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.h"
+#include "bigk.h"
 
 namespace fia {
 namespace {
 
-typedef double d4_t __attribute__((ext_vector_type(4)));
-
-// C += A B on the f64 matrix cores; lane l supplies A[l&15][l>>4] and B[l>>4][l&15],
-// and holds C[(l>>4) + 4r][l&15] in register r.
-__device__ __forceinline__ d4_t mfma4(double a, double b, d4_t c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
 typedef __attribute__((address_space(3))) void* lds_vp;         // LDS-DMA destination
 typedef const __attribute__((address_space(1))) void* glb_vp;   // ... and its global source
-
-__device__ __forceinline__ double wsum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
 
 // block-wide sum for 256-thread blocks (every thread gets the result)
 __device__ __forceinline__ double bsum256(double x, double* red) {
@@ -75,63 +61,6 @@ __device__ __forceinline__ void wave_best(double& a, int& p, double& v) {
     if (better(oa, op, a, p)) { a = oa; p = op; v = ov; }
   }
 }
-
-// ------------------------------------------------------------------------------------
-// model traits.  A side block has Ds coordinates padded to NPs = 16 T.
-//   MF  side [emb (k), bias, 0 pad]  (mf:43-65)    record [x_emb (k), x_bias, dup_other]
-//   NCF side [mlp emb (k), gmf emb (k)] (ncf:49-64) record [x_mlp (k), W3g*x_gmf (k), dup_other]
-// per-query record: [1/n, c_q, x.v, r-hat(u,i), cq_u, xv_u, cq_i, xv_i, side 0, side 1]
-// per-query work:   [n, cdup, esum, r-hat, coupled, -, -, -, v_u, v_i, theta_u, theta_i]
-// ------------------------------------------------------------------------------------
-template <int K_>
-struct BMF {
-  static constexpr int K = K_, H = 1, Ds = K + 1, NPs = K + 16, T = NPs / 16;
-  static constexpr bool ncf = false;
-  static constexpr int SB = K + 2, R = 8 + 2 * SB, QW = 8 + 4 * NPs;
-  __host__ __device__ static constexpr bool decayed(int a) { return a < K; }
-  // reference theta order [p_u, q_i, b_u, b_i]
-  __device__ static int ref_index(int side, int a) { return a < K ? side * K + a : 2 * K + side; }
-};
-
-template <int K_>
-struct BNCF {
-  static constexpr int K = K_, H = K / 2, Ds = 2 * K, NPs = 2 * K, T = NPs / 16;
-  static constexpr bool ncf = true;
-  static constexpr int SB = 2 * K + 1, R = 8 + 2 * SB, QW = 8 + 4 * NPs;
-  __host__ __device__ static constexpr bool decayed(int) { return true; }
-  // reference theta order [Pm_u, Qm_i, Pg_u, Qg_i]
-  __device__ static int ref_index(int side, int a) { return a < K ? side * K + a : 2 * K + side * K + (a - K); }
-};
-
-// Gram tile storage: tile (tr, tc), tc <= tr, in column-major tile order; inside a tile
-// element (row m, col n) at m + 16 n.
-__host__ __device__ constexpr int tile_off(int T, int tr, int tc) { return tc * T - (tc * (tc - 1)) / 2 + (tr - tc); }
-template <class M>
-constexpr int64_t gram_words() { return (int64_t)M::T * (M::T + 1) / 2 * 256; }
-
-template <class M>
-__device__ __forceinline__ double gram_at(const double* __restrict__ G, int r, int c) {
-  const int hi = r > c ? r : c, lo = r > c ? c : r;
-  return G[tile_off(M::T, hi >> 4, lo >> 4) * 256 + (hi & 15) + 16 * (lo & 15)];
-}
-
-struct BigArgs {
-  const int32_t* qu;
-  const int32_t* qi;
-  int64_t U, I;
-  const int64_t* ptr[2];
-  const int32_t* row[2];
-  const int32_t* other[2];
-  const float* rating[2];
-  const double* gram[2];
-  const double* l1[2];
-  const double* resid;
-  const double* gm[2];     // NCF g_mlp per side, by train row
-  const int32_t* slot[2];  // Gram cache slot per entity (nullptr = identity)
-  const float* t[10];
-  double wd, damping;
-  PairTable pairs;
-};
 
 // ------------------------------------------------------------------------------------
 // entities referenced by a query set (fia_prepare_for)
@@ -694,55 +623,16 @@ __global__ __launch_bounds__(256) void k_big_prologue(BigArgs A, int64_t Q, doub
 }
 
 // ------------------------------------------------------------------------------------
-// Blocked left-looking LDL^T + solve, one 512-thread workgroup per system (persistent
-// over the list).  System = one side block (CPL = false, NP = NPs) or a full coupled
-// query (CPL = true, NP = 2 NPs).  Augmented matrix rows: [0, NP) the Hessian, NP the
-// right-hand side v^T, NP+1..NP+15 zero, so row NP of L is y = D^-1 L^-1 v.
-// L (column-major, LDR = NP + 16 rows) lives in this workgroup's scratch slab.  Per
-// panel of NB columns:
-//   (a) MFMA update of the panel rows from the factored columns (L streamed, D L^T of
-//       the panel rows on the fly), result in LDS;
-//   (b) one wave factors the NB x NB diagonal block in registers (readlane broadcasts);
-//   (c) every row below solves against it in registers (barrier-free TRSM) and writes
-//       its L row segment.
-// Then L^T x = y in 32-column blocks from the end: a one-wave triangle per block and a
-// GEMV update of the earlier entries, whose L operands are loaded behind the triangle.
+// Per-query solve, one 512-thread workgroup per system (persistent over the list).
+// System = one side block (CPL = false, NP = NPs) or a full coupled query (CPL = true,
+// NP = 2 NPs); the matrix source is `aorig` (the Hessian from the Gram caches, row NP the
+// right-hand side v^T), the epilogue writes the padded solution and the scoring record.
+// The blocked LDL^T between them is the algorithm of big_ldlt_solve (bigk.h, where it is
+// described), kept in place here: calling the shared function instead compiled this kernel
+// at MF k = 256 with 1070 spilled VGPRs instead of 575 and its solve of 1,024 coupled
+// queries measured 18.2 ms instead of 12.1 ms (same MI355X, interleaved), whatever the
+// function's signature (references, by value, LDS-typed pointers, thread indices passed in).
 // ------------------------------------------------------------------------------------
-constexpr int kSolveMG = 2;     // row tiles per wave per MFMA pass
-constexpr int PD = 8;           // k-steps in flight in the panel update
-// solve workgroup (8 waves: 2 per SIMD, 256 VGPRs each -- the 32-wide register rows of
-// the diagonal block / TRSM and the prefetch ring fit without spills)
-template <int NP>
-constexpr int solve_threads() { return 512; }
-
-template <int NP>
-constexpr int solve_nb() {   // 32-column panels when NP allows and LDS fits, else 16
-  return NP % 32 == 0 && ((NP + 16) * 33 + NP + 32 * 32 + 64) * 8 <= 160 * 1024 ? 32 : 16;
-}
-template <int NP>
-constexpr size_t solve_lds() {
-  return (size_t)((NP + 16) * (solve_nb<NP>() + 1) + NP + solve_nb<NP>() * solve_nb<NP>() + 64) * 8;
-}
-
-__device__ __forceinline__ double readlane_dbl(double v, int l) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-template <int NW>
-__device__ __forceinline__ double bsum(double x, double* red) {
-  x = wsum(x);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
-  __syncthreads();
-  double t = 0.0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) t += red[w];
-  return t;
-}
-
 template <class M, int NP, bool CPL>
 __global__ __launch_bounds__(solve_threads<NP>()) void k_big_solve(BigArgs A, const int32_t* __restrict__ list,
                                                    const double* __restrict__ qwork, double* __restrict__ lscr,
@@ -1721,33 +1611,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
 // ------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------
-BigArgs make_big_args(fia_ctx* c, const int32_t* qu, const int32_t* qi) {
-  BigArgs A;
-  fill_list_args(c, A);
-  A.qu = qu;
-  A.qi = qi;
-  for (int s = 0; s < 2; ++s) {
-    A.gm[s] = c->gm[s].as<double>();
-    A.slot[s] = c->subset ? c->slot[s].as<int32_t>() : nullptr;
-  }
-  A.resid = c->resid.as<double>();
-  return A;
-}
-
-inline unsigned grid_cap(int64_t n, int64_t cap) {
-  if (n < 1) n = 1;
-  return (unsigned)(n < cap ? n : cap);
-}
-
-int cu_count(fia_ctx* c) {
-  if (c->num_cus <= 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || n <= 0) n = 256;
-    c->num_cus = n;
-  }
-  return c->num_cus;
-}
-
 // Gram work lists: slices of <= kBigSlice ratings of every cached entity, longest lists
 // first; items {entity, start, len, dst} with dst >= 0 the cache slot, dst < 0 the partial
 // slot -dst-1 of a split list; split lists get a combine entry {cache slot, first partial,
@@ -1936,6 +1799,29 @@ hipError_t launch_solve_batched(fia_ctx* c, const BigArgs& A, int64_t max_sys, c
   return hipSuccess;
 }
 
+// the per-query work words (n, pair terms, v, theta_t) of a batch and, with `solve`, x = H^-1 v
+// in c->xb: fia_query_batch's prologue and its two solve launches, for group_big.hip (`sides`
+// false: every query is known to be a train pair, so there are no side systems to launch for)
+template <class M>
+hipError_t big_systems_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, bool solve, bool sides,
+                            hipStream_t s) {
+  constexpr int NPs = M::NPs;
+  FIA_HIP_TRY(c->rec.reserve(sizeof(double) * (size_t)(Q * M::R + 1), s));
+  FIA_HIP_TRY(c->qwork.reserve(sizeof(double) * (size_t)(Q * M::QW + 1), s));
+  FIA_HIP_TRY(c->xb.reserve(sizeof(double) * (size_t)(Q * 2 * NPs + 1), s));
+  FIA_HIP_TRY(c->syslist.reserve(sizeof(int32_t) * (size_t)(2 * Q + 2), s));
+  FIA_HIP_TRY(c->cpllist.reserve(sizeof(int32_t) * (size_t)(Q + 2), s));
+  const BigArgs A = make_big_args(c, qu, qi);
+  FIA_HIP_TRY(hipMemsetAsync(c->syslist.ptr, 0, sizeof(int32_t), s));
+  FIA_HIP_TRY(hipMemsetAsync(c->cpllist.ptr, 0, sizeof(int32_t), s));
+  hipLaunchKernelGGL(k_big_prologue<M>, dim3(grid_cap(Q, 1 << 20)), dim3(256), 0, s, A, Q, c->qwork.as<double>(),
+                     c->syslist.as<int32_t>(), c->cpllist.as<int32_t>());
+  FIA_HIP_TRY(hipGetLastError());
+  if (!solve) return hipSuccess;
+  if (sides) FIA_HIP_TRY((launch_solve_batched<M, NPs>(c, A, 2 * Q, c->syslist.as<int32_t>(), s)));
+  return launch_solve<M, 2 * NPs, true>(c, A, Q, c->cpllist.as<int32_t>(), s);
+}
+
 template <class M>
 hipError_t query_big_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* offsets,
                           int64_t max_chunks, int32_t* rel_idx, double* influence, double* x_out, int K,
@@ -2025,6 +1911,14 @@ hipError_t check_cover(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* 
   hipLaunchKernelGGL(k_check_cover, dim3(grid_cap((Q + 255) / 256, 4096)), dim3(256), 0, s, Q, qu, qi, c->p.U,
                      c->p.I, c->slot[0].as<int32_t>(), c->slot[1].as<int32_t>(), flag);
   return hipGetLastError();
+}
+
+hipError_t big_systems(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, bool solve, bool sides,
+                       hipStream_t s) {
+  hipError_t e = hipErrorInvalidValue;
+  for_big_size<BMF, BNCF>(c->p.model, c->p.k,
+                          [&](auto m) { e = big_systems_impl<decltype(m)>(c, Q, qu, qi, solve, sides, s); });
+  return e;
 }
 
 hipError_t query_big(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* offsets,

@@ -279,6 +279,10 @@ struct fia_ctx {
   // the same row table, and gxq for the newton values [num_rows] of a top-K without the array)
   fia::DevBuf rowrec, gxq;
   uint64_t rowrec_version = ~0ull;
+  // the same two calls at large k (group_big.hip), per launch of a chunk of systems: the groups'
+  // scalars and right-hand side sums, their two Gram-shaped downdates (tile-packed, as the
+  // caches), and fia_self_influence's implicit queries
+  fia::DevBuf dwork, dslab, dpairs;
   // large-k path (bigk.hip): per-list-position entity, per-train-row residual / NCF backward
   // vectors, per-query Hessian inputs and solutions, solve lists and LDL^T scratch
   fia::DevBuf self[2];    // int32 [N] entity owning list position p of side s
@@ -480,8 +484,23 @@ hipError_t total_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32
                            double* total, int32_t* count, int K, int64_t* topk_idx, double* topk_val,
                            hipStream_t s);
 
+// the per-query work words of a batch (c->qwork) and, with `solve`, x = H^-1 v (c->xb): the
+// prologue and solve launches of query_big alone; sides = false when every query is a train pair
+hipError_t big_systems(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, bool solve, bool sides,
+                       hipStream_t s);
+
 // fia_group_influence (group.hip): per group of train rows the re-solved system with the
-// group's rows removed; small k only (group_supported); scratch: c->rowrec, c->gxq
+// group's rows removed; the small-k sizes (group_supported); scratch: c->rowrec, c->gxq.
+// group_influence_big / self_influence_big (group_big.hip): the same two calls for the sizes of
+// big_supported, the systems in device memory, in chunks of bounded scratch (c->dwork, c->dslab,
+// c->dpairs and the per-query buffers of query_big)
+hipError_t ensure_rowrec(fia_ctx* c, hipStream_t s);
+hipError_t group_influence_big(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi,
+                               const int64_t* grp_offsets, int64_t num_groups, const int64_t* mem_offsets,
+                               int64_t total_members, const int32_t* mem_row, double* group, double* first_order,
+                               double* dtheta, hipStream_t s);
+hipError_t self_influence_big(fia_ctx* c, int64_t n, const int32_t* rows, double* first_order, double* newton,
+                              double* error, hipStream_t s);
 bool group_supported(int model, int k);
 hipError_t group_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* grp_offsets,
                            int64_t num_groups, const int64_t* mem_offsets, int64_t total_members,

@@ -187,16 +187,22 @@ hipError_t self_influence(fia_ctx* c, int64_t n, const int32_t* rows, double* fi
         newton = c->gxq.as<double>();
       }
     }
-    const QueryArgs A = make_args(c, nullptr, nullptr);
-    SelfArgs S{};
-    S.n = n;
-    S.rows = rows;
-    S.first = first_order;
-    S.newton = newton;
-    S.error = error;
-    hipError_t e = hipErrorInvalidValue;              // (group_supported is checked by the caller)
-    dispatch_small(c->p.model, c->p.k, [&](auto m) { e = self_impl<decltype(m)>(c, A, S, s); });
-    FIA_HIP_TRY(e);
+    if (big_supported(c->p.model, c->p.k)) {
+      // the large-k models: the systems in device memory, in chunks of rows (group_big.hip); the
+      // top-K stage below reads the newton values either way
+      FIA_HIP_TRY(self_influence_big(c, n, rows, first_order, newton, error, s));
+    } else {
+      const QueryArgs A = make_args(c, nullptr, nullptr);
+      SelfArgs S{};
+      S.n = n;
+      S.rows = rows;
+      S.first = first_order;
+      S.newton = newton;
+      S.error = error;
+      hipError_t e = hipErrorInvalidValue;            // (the sizes are checked by the caller)
+      dispatch_small(c->p.model, c->p.k, [&](auto m) { e = self_impl<decltype(m)>(c, A, S, s); });
+      FIA_HIP_TRY(e);
+    }
   }
   if (K <= 0) return hipSuccess;
   if (n > 0) {

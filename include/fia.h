@@ -314,9 +314,21 @@ int fia_total_influence(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user
  * Batch limit: num_groups <= FIA_GROUP_MAX_GROUPS and total_members <= FIA_GROUP_MAX_MEMBERS
  * (2^31 - 1 each): a larger batch is refused with FIA_ERR_INVALID before anything is reserved or
  * launched -- split it.
- * Sizes: MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32}, whose full packed system fits in LDS.
- * The large-k models (MF k >= 128, NCF k >= 64) keep their systems in device memory: for them the
- * call returns FIA_ERR_UNSUPPORTED. */
+ * Sizes: every size fia_query_batch is built for.  MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32}
+ * keep the full packed system of a group in LDS.  The large-k models (MF k in {128, 256}, NCF k in
+ * {64, 128, 256}) keep it in device memory: a group is two Gram-shaped downdates in the caches'
+ * tile layout (2 * T (T + 1) / 2 * 256 doubles, T = ceil(side block / 16): 0.16 MB at MF k=128,
+ * 2.2 MB at NCF k=256), four scalars and a right-hand side, solved by fia_query_batch's coupled
+ * blocked LDL^T.  Those downdates are context scratch bounded at 1 GiB per launch: a longer batch
+ * runs in chunks of groups on `stream`, still without host synchronisation, and the results do not
+ * depend on the chunking.  There, after fia_prepare_for, the groups of a query outside the cover
+ * score NaN (as its influences do in fia_query_batch; fia_count_related with a total is the call
+ * that refuses such a batch): the members' residuals exist only for covered entities, and nothing
+ * of such a group's members is read.  Any other size is FIA_ERR_UNSUPPORTED.
+ * The environment variable FIA_BIGK_CHUNK (a positive integer) lowers the large-k chunk length of
+ * this call and of fia_self_influence to that many systems per launch: a testing knob; a value
+ * above the scratch-derived length is ignored.
+ * fia_version stays 100 with these sizes added: no signature, struct or constant changed. */
 #define FIA_GROUP_MAX_GROUPS ((1LL << 31) - 1)
 #define FIA_GROUP_MAX_MEMBERS ((1LL << 31) - 1)
 int fia_group_influence(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item,
@@ -369,8 +381,11 @@ int fia_group_influence(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user
  * pending small-k Gram pass as fia_group_influence does (and, like it, cannot start a capture
  * before that join).  Checks run in fia_group_influence's order: bounds, state, outputs, the empty
  * batch, nulls, support.
- * Sizes: those of fia_group_influence (MF k in {8, 16, 32, 64}, NCF k in {8, 16, 32}); anything
- * else is FIA_ERR_UNSUPPORTED. */
+ * Sizes: those of fia_group_influence; anything else is FIA_ERR_UNSUPPORTED.  At the large-k sizes
+ * (MF k in {128, 256}, NCF k in {64, 128, 256}) the rows run in chunks of 4096 on `stream` (the
+ * per-row work words, 8 + 4 * padded side block doubles, and the solutions of a chunk are context
+ * scratch: 100 MB at NCF k=256); a row's own downdate needs no slab, error comes from the
+ * residuals fia_prepare keeps per train row, and the results do not depend on the chunking. */
 #define FIA_SELF_MAX_ROWS ((1LL << 31) - 1)
 int fia_self_influence(fia_ctx* ctx,
                        int64_t num_rows,
