@@ -258,6 +258,7 @@ struct fia_ctx {
   // the side-system solve and finished by k_solve.  Zero when (re)allocated; k_solve takes the
   // count and counts itself a reader with one 64-bit atomic on the first two words, and its last
   // reader zeroes both, so every call finds the count zero without a memset or a launch
+  // (MF k = 16 never touches it: its coupled queries are a role of k_solve_quad)
   fia::DevBuf coupled;
   // query groups per entity (entity-shared scoring): global entity index g = e (users) or
   // U + e (items)

@@ -103,16 +103,72 @@ __device__ void solve_epilogue(const QueryArgs& A, int64_t q, int32_t u, int32_t
   }
 }
 
+// The full D x D system of one query on ONE WAVE: prologue, packed Hessian, LDL^T, record.  The
+// wave may be a 64-thread workgroup (k_solve) or one wave of a larger one (the coupled role of
+// k_solve_quad): its LDS is the caller's slab of kFullSlab<M> doubles, its synchronisation is
+// wave-level (solve.h, WV = true), and it reads nothing another wave writes.  w / sW1 / sb1:
+// the NCF weights the caller staged (dummies for MF).
+template <class M>
+constexpr int kFullSlab = M::D * (M::D + 1) / 2 + 5 * M::D + 4 * M::K + 8;
+template <class M>
+__device__ __forceinline__ void solve_full_wave(const QueryArgs& A, int64_t q, double* __restrict__ rec,
+                                                double* __restrict__ x_out, double* __restrict__ slab,
+                                                const NCFWeights<M::ncf ? M::K : 2>& w,
+                                                const double* __restrict__ sW1, const double* __restrict__ sb1) {
+  constexpr int Ds = M::Ds, D = M::D;
+  double* const H = slab;
+  double* const v = H + D * (D + 1) / 2;
+  double* const g = v + D;
+  double* const th = g + D;
+  double* const dd = th + D;
+  double* const ww = dd + D;
+  double* const sh = ww + D;
+  wave_lds_sync();               // the slab's previous query is read out
+  const int lane = threadIdx.x & 63;
+  const int32_t u = A.qu[q], i = A.qi[q];
+  double* R = rec + q * M::R;
+  const bool ok_id = (u >= 0 && u < A.U && i >= 0 && i < A.I);
+  const int64_t ub = ok_id ? A.ptr[0][u] : 0, du = ok_id ? A.ptr[0][u + 1] - ub : 0;
+  const int64_t ib = ok_id ? A.ptr[1][i] : 0, di = ok_id ? A.ptr[1][i + 1] - ib : 0;
+  const int64_t n = du + di;
+  if (n == 0) {
+    if (x_out)
+      for (int a = lane; a < D; a += kSolveThreads) x_out[q * D + a] = NAN;
+    if (lane == 0) R[0] = NAN;
+    return;
+  }
+
+  const double rhat_ui = solve_prologue<M, kSolveThreads, true>(A, u, i, th, g, sh, w, sW1, sb1);
+
+  // ---- assemble H (solve.h) and solve ----
+  {
+    const bool coupled = assemble_hessian<M, true>(A, u, i, n, rhat_ui, g, H);
+    for (int a = lane; a < D; a += kSolveThreads) v[a] = g[a];
+    wave_lds_sync();
+
+    if (coupled) {
+      ldlt_solve<D, true>(H, v, dd, ww, 0, D);
+    } else {
+      ldlt_solve<D, true>(H, v, dd, ww, 0, Ds);
+      ldlt_solve<D, true>(H, v, dd, ww, Ds, D);
+    }
+    wave_lds_sync();
+  }
+
+  solve_epilogue<M>(A, q, u, i, n, rhat_ui, th, g, v, w, R, x_out);
+}
+
 // One wave per query, the full D x D packed LDL^T: the queries whose test pair is a train row
 // (its Hessian couples the user and item blocks; the side-system solves list them in qlist
 // {count, q_0, q_1, ...}).  The word before the count counts this kernel's workgroups as they
 // read it: one 64-bit atomic on {readers, count} returns the count and the number of earlier
 // readers, and the last reader zeroes both words -- the list is empty again for the next call's
 // side-system solve, with no memset and no launch (and the same under a replayed graph).
+// (MF k = 16 never lists one: its coupled queries are a role of k_solve_quad.)
 template <class M>
 __global__ __launch_bounds__(kSolveThreads, (M::Ds <= 33 ? 2 : 1)) void k_solve(QueryArgs A, int64_t Q, double* __restrict__ rec,
                                                          double* __restrict__ x_out, int32_t* __restrict__ qlist) {
-  constexpr int K = M::K, Ds = M::Ds, D = M::D;
+  constexpr int K = M::K;
   static_assert(kSolveThreads == 64, "one wave: lane 0's atomic is broadcast by a shuffle");
   unsigned long long rw = 0;
   {
@@ -124,9 +180,7 @@ __global__ __launch_bounds__(kSolveThreads, (M::Ds <= 33 ? 2 : 1)) void k_solve(
     }
     rw = __shfl(rw, 0);
   }
-  __shared__ double H[D * (D + 1) / 2];
-  __shared__ double v[D], g[D], th[D], dd[D], ww[D];
-  __shared__ double sh[4 * K + 8];
+  __shared__ double slab[kFullSlab<M>];
   // NCF weights staged once per block (fp64), read by every query the block solves
   __shared__ NCFWeights<M::ncf ? K : 2> w;
   __shared__ double sW1[M::ncf ? 2 * K * K : 1];
@@ -137,42 +191,8 @@ __global__ __launch_bounds__(kSolveThreads, (M::Ds <= 33 ? 2 : 1)) void k_solve(
     for (int t = threadIdx.x; t < K; t += blockDim.x) sb1[t] = (double)A.t[5][t];
   }
   const int64_t nwork = (int64_t)(rw >> 32);
-  for (int64_t wk = blockIdx.x; wk < nwork; wk += gridDim.x) {
-  __syncthreads();
-  const int64_t q = qlist[1 + wk];
-  const int lane = threadIdx.x;
-  const int32_t u = A.qu[q], i = A.qi[q];
-  double* R = rec + q * M::R;
-  const bool ok_id = (u >= 0 && u < A.U && i >= 0 && i < A.I);
-  const int64_t ub = ok_id ? A.ptr[0][u] : 0, du = ok_id ? A.ptr[0][u + 1] - ub : 0;
-  const int64_t ib = ok_id ? A.ptr[1][i] : 0, di = ok_id ? A.ptr[1][i + 1] - ib : 0;
-  const int64_t n = du + di;
-  if (n == 0) {
-    if (x_out)
-      for (int a = lane; a < D; a += kSolveThreads) x_out[q * D + a] = NAN;
-    if (lane == 0) R[0] = NAN;
-    continue;
-  }
-
-  const double rhat_ui = solve_prologue<M, kSolveThreads>(A, u, i, th, g, sh, w, sW1, sb1);
-
-  // ---- assemble H (solve.h) and solve ----
-  {
-    const bool coupled = assemble_hessian<M>(A, u, i, n, rhat_ui, g, H);
-    for (int a = lane; a < D; a += kSolveThreads) v[a] = g[a];
-    __syncthreads();
-
-    if (coupled) {
-      ldlt_solve<D>(H, v, dd, ww, 0, D);
-    } else {
-      ldlt_solve<D>(H, v, dd, ww, 0, Ds);
-      ldlt_solve<D>(H, v, dd, ww, Ds, D);
-    }
-    __syncthreads();
-  }
-
-  solve_epilogue<M>(A, q, u, i, n, rhat_ui, th, g, v, w, R, x_out);
-  }   // work loop
+  for (int64_t wk = blockIdx.x; wk < nwork; wk += gridDim.x)
+    solve_full_wave<M>(A, (int64_t)qlist[1 + wk], rec, x_out, slab, w, sW1, sb1);
 }
 
 // Scoring records from a GIVEN inverse HVP (fia_query_batch_x: the reference's cached
@@ -1238,8 +1258,7 @@ __device__ __forceinline__ void quad_back(Quad16& Z, const double (&z)[4], doubl
 // of the launch writes
 template <class M>
 __device__ __forceinline__ void solve_quad_wave(const QueryArgs& A, int64_t Q, double* __restrict__ rec,
-                                                double* __restrict__ x_out, int32_t* __restrict__ coupled,
-                                                int64_t wv) {
+                                                double* __restrict__ x_out, int64_t wv) {
   static_assert(!M::ncf && M::K == 16, "MF k = 16");
   constexpr int K = M::K, Ds = M::Ds, D = M::D, GS = Ds * (Ds + 1) / 2, GSP = (GS + 1) & ~1;
   const int lane = threadIdx.x & 63, qd = lane >> 2, j = lane & 3, h = qd >> 1, sd = qd & 1;
@@ -1320,13 +1339,7 @@ __device__ __forceinline__ void solve_quad_wave(const QueryArgs& A, int64_t Q, d
     if (sd == 0 && j == 0) rec[q * M::R] = NAN;
     return;
   }
-  if (cdup > 0.0) {               // the test pair is a train row: the full-D k_solve finishes it
-    if (sd == 0 && j == 0) {
-      const int slot = atomicAdd(coupled, 1);
-      coupled[1 + slot] = (int32_t)q;
-    }
-    return;
-  }
+  if (cdup > 0.0) return;         // the test pair is a train row: the coupled role's (full D)
   double* __restrict__ R = rec + q * M::R;
   if (sd == 0 && j == 0) {
     R[0] = 1.0 / (double)n;
@@ -1363,18 +1376,75 @@ __device__ __forceinline__ void solve_quad_wave(const QueryArgs& A, int64_t Q, d
 // nothing any other workgroup writes; a scan-role workgroup waits only on the tile words of
 // EARLIER tickets, and a ticket is drawn by a workgroup that has already started -- so whatever
 // order the dispatcher starts the roles in, every awaited workgroup is resident and runs to its
-// publish without waiting on a later one.  The `coupled` count the solve role appends to is not
-// touched by the scan role (the scan's zero_word is null here): k_solve leaves it zero.
+// publish without waiting on a later one.
+// The last coupled_groups(Q) workgroups are the COUPLED role: the queries whose test pair is a
+// train row (the solve role leaves them unwritten).  Workgroup w of the role tests queries
+// w, w + groups, ... (kScanThreads at a time, the probe the solve role makes), compacts the hits
+// in LDS and solves them full-D, one wave per query on kCplWaves waves (solve_full_wave, the
+// body of k_solve), on slabs laid over the scan role's static LDS object -- the launch's LDS
+// stays the scan's.  It reads the Gram caches, the parameters and the pair table and writes
+// records and x_out rows no other role writes: it waits on no other workgroup either.  So the
+// fused path has no `coupled` list and no k_solve launch (usually a role that finds nothing:
+// that launch cost 5 us between the solve and the scoring kernel to draw a count of zero), and
+// the list's {readers, count} words stay zero for the paths that keep it.
+constexpr int kCplWaves = 4, kCplGroups = 32;
+inline int64_t coupled_groups(int64_t Q) {
+  const int64_t g = (Q + kCplWaves - 1) / kCplWaves;
+  return g < kCplGroups ? g : kCplGroups;
+}
+template <class M>
+struct CoupledLds {
+  double slab[kCplWaves][kFullSlab<M>];
+  NCFWeights<M::ncf ? M::K : 2> w;       // (MF: never read)
+  double sW1[1], sb1[1];
+  int32_t hits[kScanThreads];
+  int32_t nhit;
+};
+template <class M>
+__device__ __forceinline__ void coupled_role(const QueryArgs& A, int64_t Q, double* __restrict__ rec,
+                                             double* __restrict__ x_out, int64_t wg, int64_t nwg) {
+  static_assert(!M::ncf, "MF: no weights staged");
+  static_assert(sizeof(CoupledLds<M>) <= sizeof(ScanFillLds) && alignof(CoupledLds<M>) <= alignof(ScanFillLds),
+                "the coupled role's LDS lies inside the scan role's");
+  CoupledLds<M>* const L = reinterpret_cast<CoupledLds<M>*>(scan_fill_lds<1>());
+  const int wave = threadIdx.x >> 6;
+  // (the trip count is the workgroup's: every thread reaches every barrier)
+  for (int64_t first = wg; first < Q; first += (int64_t)kScanThreads * nwg) {
+    if (threadIdx.x == 0) L->nhit = 0;
+    __syncthreads();
+    const int64_t q = first + (int64_t)threadIdx.x * nwg;
+    if (q < Q) {
+      const int32_t u = A.qu[q], i = A.qi[q];
+      if (related_count(A, u, i) > 0) {
+        double cdup = 0.0, rsum = 0.0;
+        A.pairs.lookup((unsigned long long)u * (unsigned long long)A.I + (unsigned long long)i, cdup, rsum);
+        if (cdup > 0.0) L->hits[atomicAdd(&L->nhit, 1)] = (int32_t)threadIdx.x;
+      }
+    }
+    __syncthreads();
+    const int nh = L->nhit;
+    if (wave < kCplWaves)
+      for (int h = wave; h < nh; h += kCplWaves)
+        solve_full_wave<M>(A, first + (int64_t)L->hits[h] * nwg, rec, x_out, L->slab[wave], L->w, L->sW1, L->sb1);
+    __syncthreads();
+  }
+}
+
 template <class M>
 __global__ __launch_bounds__(kScanThreads) void k_solve_quad(ScanArgs S, QueryArgs A, double* __restrict__ rec,
-                                                             double* __restrict__ x_out,
-                                                             int32_t* __restrict__ coupled) {
+                                                             double* __restrict__ x_out) {
   const unsigned ntiles = (unsigned)((S.Q + 1 + kScanTile - 1) / kScanTile);
   if (blockIdx.x < ntiles) {
     query_scan_body<1>(S);
     return;
   }
-  solve_quad_wave<M>(A, S.Q, rec, x_out, coupled,
+  const unsigned nsolve = (unsigned)((S.Q + 63) / 64);
+  if (blockIdx.x - ntiles >= nsolve) {
+    coupled_role<M>(A, S.Q, rec, x_out, (int64_t)(blockIdx.x - ntiles - nsolve),
+                    (int64_t)(gridDim.x - ntiles - nsolve));
+    return;
+  }
+  solve_quad_wave<M>(A, S.Q, rec, x_out,
                      (int64_t)(blockIdx.x - ntiles) * (kScanThreads / 64) + (threadIdx.x >> 6));
 }
 
@@ -2524,6 +2594,71 @@ __global__ __launch_bounds__(256) void k_topk_merge_thread(
   }
 }
 
+// K = 1 of the above on a 16-lane ROW per query (a wave takes four): the thread-per-query walk
+// is a chain of about six dependent round trips (coff -> uptr -> ~9 slots 4 at a time ->
+// urow/irow), here it is three: {coff, qu, qi}, then {uptr, iptr, every slot of the row: lane l
+// takes slots cb + l, cb + l + 16, ...} together, then the row lookup.  Both words of a slot are
+// loaded unconditionally (a slot past the query's end reads slot 0, always reserved, and
+// counts as empty), kMergeRowRounds rounds issued before any use.  The lanes' bests meet in the
+// row rotations of wave_best: `better` is a strict total order on (key, position), so the
+// winner is the one the serial walk finds.  No lane leaves before the rotations.
+// Taken up to kMergeRowMaxQ queries (a quarter of a wave per query: 4,096 waves there, half of
+// what the chip holds): ml-1m-ex, 12,074 queries, 8.04 -> 4.42 us.  Beyond it the rows fill every
+// wave slot for the length of the kernel -- yelp-ex, 51,153 queries = 12.8 k waves: 8.24 -> 7.41 us
+// alone, but the step with two batches in flight did not gain (0.4868 -> 0.4887 ms, medians of 5
+// and 4 alternating runs, inside the parent's spread): the other batch's kernels wait for the
+// slots -- so larger batches keep the thread per query (profiles/step_tail.md).
+constexpr int kMergeRowRounds = 2;
+constexpr int64_t kMergeRowMaxQ = 16384;
+__global__ __launch_bounds__(256) void k_topk_merge_row(
+    const int32_t* __restrict__ qu, const int32_t* __restrict__ qi, int64_t Q, const int64_t* __restrict__ coff,
+    int spc, const int32_t* __restrict__ cand_pos, const double* __restrict__ cand_val,
+    const int64_t* __restrict__ uptr, const int32_t* __restrict__ urow, const int64_t* __restrict__ iptr,
+    const int32_t* __restrict__ irow, int64_t U, int64_t I, int64_t* __restrict__ topk_pos,
+    int64_t* __restrict__ topk_idx, double* __restrict__ topk_val) {
+  const int l = threadIdx.x & 15;
+  const int64_t q0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
+  const bool act = q0 < Q;
+  const int64_t q = act ? q0 : Q - 1;
+  const int64_t cb = coff[q] * spc, ce = coff[q + 1] * spc;
+  const int32_t u = qu[q], i = qi[q];
+  int p2[kMergeRowRounds];
+  double v2[kMergeRowRounds];
+#pragma unroll
+  for (int r = 0; r < kMergeRowRounds; ++r) {
+    const int64_t c = cb + l + 16 * r;
+    const int64_t cc = c < ce ? c : 0;
+    p2[r] = cand_pos[cc];
+    v2[r] = cand_val[cc];
+    if (c >= ce) p2[r] = -1;
+  }
+  const bool ok_id = (u >= 0 && u < U && i >= 0 && i < I);
+  const int64_t ub = ok_id ? uptr[u] : 0, du = ok_id ? uptr[u + 1] - ub : 0, ib = ok_id ? iptr[i] : 0;
+  double ba = -2.0, bv = 0.0;
+  int bp = 0x7fffffff;
+#pragma unroll
+  for (int r = 0; r < kMergeRowRounds; ++r) {
+    const double a = topk_key(v2[r]);
+    if (p2[r] >= 0 && better(a, p2[r], ba, bp)) { ba = a; bp = p2[r]; bv = v2[r]; }
+  }
+  for (int64_t c = cb + l + 16 * kMergeRowRounds; c < ce; c += 16) {
+    const int p = cand_pos[c];
+    const double vv = cand_val[c];
+    const double a = topk_key(vv);
+    if (p >= 0 && better(a, p, ba, bp)) { ba = a; bp = p; bv = vv; }
+  }
+  best_dpp_step<0x128>(ba, bp, bv);   // row_ror:8
+  best_dpp_step<0x124>(ba, bp, bv);   // row_ror:4
+  best_dpp_step<0x122>(ba, bp, bv);   // row_ror:2
+  best_dpp_step<0x121>(ba, bp, bv);   // row_ror:1 -- every lane of the row holds the query's best
+  if (act && l == 0) {
+    const bool ok = ba > -1.5;
+    topk_pos[q] = ok ? bp : -1;
+    topk_idx[q] = ok ? (int64_t)(bp < du ? urow[ub + bp] : irow[ib + (bp - du)]) : -1;
+    topk_val[q] = ok ? bv : NAN;
+  }
+}
+
 // ------------------------------------------------------------------------------------
 // host-side dispatch
 // ------------------------------------------------------------------------------------
@@ -2744,14 +2879,15 @@ hipError_t query_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
   const int64_t max_items = max_chunks;
   // the queries whose test pair is a train row are listed in `coupled` {count, q...} by the
   // solve and finished full-D by k_solve, whose last reader leaves {readers, count} zero (the
-  // word pair in front of the list: fia_ctx::coupled); zero when (re)allocated
+  // word pair in front of the list: fia_ctx::coupled); zero when (re)allocated.  (MF k = 16
+  // neither appends nor reads: its coupled queries are a role of k_solve_quad.)
   if (c->coupled.bytes < sizeof(int32_t) * (size_t)(Q + 2) || !c->coupled.ptr) {
     FIA_HIP_TRY(c->coupled.reserve(sizeof(int32_t) * (size_t)(Q + 2), s));
     FIA_HIP_TRY(hipMemsetAsync(c->coupled.ptr, 0, c->coupled.bytes, s));
   }
   int32_t* const coupled = c->coupled.as<int32_t>() + 1;
-  // MF k = 16: the chunk scan and the side-system solves are one launch (k_solve_quad), timed
-  // with the coupled solve as the solve phase -- the chunk phase then records nothing.  Without
+  // MF k = 16: the chunk scan, the side-system solves and the coupled solves are one launch
+  // (k_solve_quad), timed as the solve phase -- the chunk phase then records nothing.  Without
   // a solve (a given x, an empty batch) the chunk phase is the one scan kernel.  Either way the
   // events are stamped by those kernels' dispatches (a marker packet per event idled the GPU
   // ~5 us: RQ2's single query), and a pair is taken only once its launch is known to proceed.
@@ -2764,8 +2900,8 @@ hipError_t query_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
   // kRunUserCost per descriptor slot), the surplus waves exit at once
   constexpr int64_t lam = kRunLambda;
   const int64_t runs_grid = (kRunUserCost * (max_chunks + 1)) / lam + 2;
-  // (the fused launch's solve role appends to the count while its scan role runs: the scan
-  // zeroes it only where it is a launch of its own, ahead of the solve)
+  // (the scan zeroes the coupled count only where it is a launch of its own, ahead of a solve
+  // that appends to it; the fused launch has no list)
   ScanArgs S;
   FIA_HIP_TRY(chunk_scan_args(c, Q, qu, qi, offsets, max_chunks, grouped, s, fused ? nullptr : coupled, runs, (int)lam,
                               M::ncf ? kNcfRunChunk : kRunChunk, S));
@@ -2814,11 +2950,11 @@ hipError_t query_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
   // non-coupled queries: thread-per-system (MF k <= 16) or column-parallel blocks
   if (Q > 0 && !x_in) {
     if constexpr (use_quad_solve<M>()) {
-      // scan_tiles(Q) scan workgroups, then 64 queries per solve workgroup; the solve phase's
-      // start is this dispatch, its end k_solve's
+      // scan_tiles(Q) scan workgroups, then 64 queries per solve workgroup, then the coupled
+      // role's; the solve phase is this one dispatch, which stamps both of its events
       sspan = phase_span(c, 1);
-      hipExtLaunchKernelGGL(k_solve_quad<M>, dim3((unsigned)(scan_tiles(Q) + (Q + 63) / 64)), dim3(kScanThreads), 0, s,
-                            sspan.a, (hipEvent_t) nullptr, 0, S, A, c->rec.as<double>(), x_out, coupled);
+      hipExtLaunchKernelGGL(k_solve_quad<M>, dim3((unsigned)(scan_tiles(Q) + (Q + 63) / 64 + coupled_groups(Q))),
+                            dim3(kScanThreads), 0, s, sspan.a, sspan.b, 0, S, A, c->rec.as<double>(), x_out);
     } else if constexpr (use_tps<M>()) {
       hipLaunchKernelGGL(k_solve_tps<M>, dim3((unsigned)((2 * Q + 63) / 64)), dim3(64), 0, s, A, Q,
                          c->rec.as<double>(), x_out, coupled);
@@ -2843,16 +2979,21 @@ hipError_t query_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
       return es;
     }
     // usually no coupled query: a small grid that exits (a full grid for the large full-D
-    // systems of k >= 32, should many test pairs be train rows).  (Folding this into the last
-    // workgroup of k_solve_tps -- an atomic finish count -- made that kernel 14 us slower at
-    // ml-1m-ex: the full-D solve's LDS and registers in every workgroup)
-    const int64_t gc = M::K <= 16 ? 64 : 256;
-    const int64_t g2 = Q < gc ? Q : gc;
-    hipExtLaunchKernelGGL(k_solve<M>, dim3((unsigned)g2), dim3(kSolveThreads), 0, s, (hipEvent_t) nullptr,
-                          sspan.b, 0, A, Q, c->rec.as<double>(), x_out, coupled);
-    if (const hipError_t es = hipGetLastError(); es != hipSuccess) {
-      phase_drop(c, 1, sspan);
-      return es;
+    // systems of k >= 32, should many test pairs be train rows).  MF k = 16 has no such launch:
+    // the coupled queries are a role of k_solve_quad, in workgroups of their own.  (Folding the
+    // full-D solve into the last workgroup of k_solve_tps -- an atomic finish count -- made that
+    // kernel 14 us slower at ml-1m-ex: its LDS and registers in EVERY workgroup, and a wait on
+    // all of them.  The role waits on nobody, its LDS lies inside the scan role's and the
+    // launch keeps the side solve's registers.)
+    if constexpr (!use_quad_solve<M>()) {
+      const int64_t gc = M::K <= 16 ? 64 : 256;
+      const int64_t g2 = Q < gc ? Q : gc;
+      hipExtLaunchKernelGGL(k_solve<M>, dim3((unsigned)g2), dim3(kSolveThreads), 0, s, (hipEvent_t) nullptr,
+                            sspan.b, 0, A, Q, c->rec.as<double>(), x_out, coupled);
+      if (const hipError_t es = hipGetLastError(); es != hipSuccess) {
+        phase_drop(c, 1, sspan);
+        return es;
+      }
     }
   }
   if constexpr (mask_path<M>()) {
@@ -2927,6 +3068,15 @@ hipError_t launch_topk_merge(fia_ctx* c, int64_t Q, const int32_t* qu, const int
   if (K <= 0 || Q <= 0) return hipSuccess;
   // a thread per query while the queries have few chunks (<= 16 on average: ml-1m-ex,
   // yelp-ex); a wave per query over long candidate lists (20M: ~170 chunks per query)
+  if (K == 1 && max_chunks <= 16 * Q && Q <= kMergeRowMaxQ) {
+    // a 16-lane row per query: three dependent round trips where the thread's walk has ~six
+    hipLaunchKernelGGL(k_topk_merge_row, dim3((unsigned)((Q * 16 + 255) / 256)), dim3(256), 0, s, qu, qi, Q,
+                       c->coff.as<int64_t>(), spc, c->cand_pos.as<int32_t>(), c->cand_val.as<double>(),
+                       c->idx.side[0].ptr.as<int64_t>(), c->idx.side[0].row.as<int32_t>(),
+                       c->idx.side[1].ptr.as<int64_t>(), c->idx.side[1].row.as<int32_t>(), c->p.U, c->p.I, topk_pos,
+                       topk_idx, topk_val);
+    return hipGetLastError();
+  }
   if (K <= 4 && max_chunks <= 16 * Q) {
     hipLaunchKernelGGL(k_topk_merge_thread, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s, qu, qi, Q,
                        c->coff.as<int64_t>(), K, spc, c->cand_pos.as<int32_t>(), c->cand_val.as<double>(),

@@ -10,36 +10,49 @@
 
 namespace fia {
 
+// WV = false: the system's wave is a 64-thread workgroup (lane = threadIdx.x, workgroup barriers).
+// WV = true: one wave of a larger workgroup on LDS arrays of its own (lane = threadIdx.x & 63,
+// wave_lds_sync: a wave's LDS accesses complete in order, the fence keeps the compiler from
+// moving them across) -- the same arithmetic in the same order, so the same bits.
+template <bool WV>
+__device__ __forceinline__ int solve_lane() {
+  return WV ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
+}
+template <bool WV>
+__device__ __forceinline__ void solve_sync() {
+  if constexpr (WV) wave_lds_sync(); else __syncthreads();
+}
+
 // In-place LDL^T of the packed lower block [lo, hi) followed by L D L^T x = v.
-template <int D>
+template <int D, bool WV = false>
 __device__ void ldlt_solve(double* H, double* v, double* d, double* w, int lo, int hi) {
-  const int lane = threadIdx.x;
+  const int lane = solve_lane<WV>();
   for (int j = lo; j < hi; ++j) {
     for (int c = lo + lane; c < j; c += kSolveThreads) w[c] = H[tri(j, c)] * d[c];
-    __syncthreads();
+    solve_sync<WV>();
     for (int r = j + lane; r < hi; r += kSolveThreads) {
       const double* Lr = H + tri(r, 0);
       double t = Lr[j];
       for (int c = lo; c < j; ++c) t = fma(-Lr[c], w[c], t);
       if (r == j) d[j] = t; else H[tri(r, j)] = t;
     }
-    __syncthreads();
+    solve_sync<WV>();
     const double dj = d[j];
     for (int r = j + 1 + lane; r < hi; r += kSolveThreads) H[tri(r, j)] /= dj;
-    __syncthreads();
+    solve_sync<WV>();
   }
   for (int j = lo; j < hi; ++j) {
     const double yj = v[j];
     for (int r = j + 1 + lane; r < hi; r += kSolveThreads) v[r] = fma(-H[tri(r, j)], yj, v[r]);
-    __syncthreads();
+    solve_sync<WV>();
   }
   for (int j = lo + lane; j < hi; j += kSolveThreads) v[j] /= d[j];
-  __syncthreads();
+  solve_sync<WV>();
   for (int j = hi - 1; j >= lo; --j) {
     const double xj = v[j];
     const double* Lj = H + tri(j, 0);
     for (int c = lo + lane; c < j; c += kSolveThreads) v[c] = fma(-Lj[c], xj, v[c]);
-    __syncthreads();
+    solve_sync<WV>();
   }
 }
 
@@ -47,12 +60,13 @@ __device__ void ldlt_solve(double* H, double* v, double* d, double* w, int lo, i
 // theta_t, v = d r(u,i)/d theta_t (gnn:155, mf:194,201 / ncf:222,229) and r-hat(u,i) of one
 // query into the workgroup's LDS arrays th[D] / g[D] (NTH threads cooperate; r-hat is
 // valid in the first wave)
-template <class M, int NTH>
+template <class M, int NTH, bool WV = false>
 __device__ double solve_prologue(const QueryArgs& A, int32_t u, int32_t i, double* __restrict__ th,
                                  double* __restrict__ g, double* __restrict__ sh, const NCFWeights<M::ncf ? M::K : 2>& w,
                                  const double* __restrict__ sW1, const double* __restrict__ sb1) {
   constexpr int K = M::K, Ds = M::Ds;
-  const int lane = threadIdx.x;
+  static_assert(!WV || NTH == 64, "one wave");
+  const int lane = solve_lane<WV>();
   double rhat_ui = 0.0;
   if constexpr (!M::ncf) {
     const float* P = A.t[0];
@@ -69,7 +83,7 @@ __device__ double solve_prologue(const QueryArgs& A, int32_t u, int32_t i, doubl
       g[K] = 1.0;
       g[Ds + K] = 1.0;
     }
-    __syncthreads();
+    solve_sync<WV>();
     double part = 0.0;
     for (int a = lane; a < K; a += NTH) part += th[a] * th[Ds + a];
     rhat_ui = wave_sum(part) + th[K] + th[Ds + K] + (double)A.t[4][0];
@@ -89,7 +103,7 @@ __device__ double solve_prologue(const QueryArgs& A, int32_t u, int32_t i, doubl
       th[Ds + K + a] = Qg[(int64_t)i * K + a];
       z1[a] = A.l1[0][(int64_t)u * K + a] + A.l1[1][(int64_t)i * K + a] + sb1[a];
     }
-    __syncthreads();
+    solve_sync<WV>();
     double mlp_part = 0.0;
     for (int dd2 = lane; dd2 < H2; dd2 += NTH) {
       double z2 = w.b2[dd2];
@@ -101,13 +115,13 @@ __device__ double solve_prologue(const QueryArgs& A, int32_t u, int32_t i, doubl
     double gmf_part = 0.0;
     for (int a = lane; a < K; a += NTH) gmf_part += w.W3[H2 + a] * th[K + a] * th[Ds + K + a];
     rhat_ui = wave_sum(mlp_part + gmf_part) + (double)A.t[9][0];
-    __syncthreads();
+    solve_sync<WV>();
     for (int c = lane; c < K; c += NTH) {
       double t = 0.0;
       for (int dd2 = 0; dd2 < H2; ++dd2) t = fma(w.W2[c * H2 + dd2], d2[dd2], t);
       d1[c] = z1[c] > 0.0 ? t : 0.0;
     }
-    __syncthreads();
+    solve_sync<WV>();
     for (int a = lane; a < 2 * K; a += NTH) {
       // rows a < K: W1[:k] (Pm part, user block); rows a >= K: W1[k:] (Qm part, item block)
       double s = 0.0;
@@ -119,7 +133,7 @@ __device__ double solve_prologue(const QueryArgs& A, int32_t u, int32_t i, doubl
       g[Ds + K + a] = w.W3[H2 + a] * th[K + a];        // d r/d Qg_i = W3g * Pg_u
     }
   }
-  __syncthreads();
+  solve_sync<WV>();
   return rhat_ui;
 }
 
@@ -128,11 +142,11 @@ __device__ double solve_prologue(const QueryArgs& A, int32_t u, int32_t i, doubl
 //   H = (2/n) (A_u (+) B_i) + the (u, i) train rows' second copies and coupling + wd M + damping I
 // One wave; the caller synchronises before reading H.  Returns whether (u, i) is a train
 // row (then the user and item blocks are coupled).
-template <class M>
+template <class M, bool WV = false>
 __device__ __forceinline__ bool assemble_hessian(const QueryArgs& A, int32_t u, int32_t i, int64_t n, double rhat_ui,
                                                  const double* __restrict__ g, double* __restrict__ H) {
   constexpr int K = M::K, Ds = M::Ds, D = M::D, GS = Ds * (Ds + 1) / 2;
-  const int lane = threadIdx.x;
+  const int lane = solve_lane<WV>();
   const double s2n = 2.0 / (double)n;
   // ---- the (u,i) pair among the train rows (pair set built with the index) ----
   double cdup, rsum;
