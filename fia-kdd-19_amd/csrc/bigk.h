@@ -1,15 +1,16 @@
-// Large-k FIA path, the pieces shared by its translation units (bigk.hip: caches, per-query
-// solves, scoring; group_big.hip: the downdated solves of fia_group_influence and
+// Large-k FIA path, the pieces shared by its translation units (bigk.hip: the host side;
+// bigk_prepare.hip, bigk_solve.hip, bigk_solve_batched.hip, bigk_score.hip: the kernels of each
+// phase behind their launchers; group_big.hip: the downdated solves of fia_group_influence and
 // fia_self_influence): model traits, the Gram tile layout, the kernels' argument struct, the
-// solve constants and the blocked LDL^T of one system in a workgroup's scratch slab.
+// solve constants, the blocked LDL^T of one system in a workgroup's scratch slab, and the
+// launchers' declarations.
 #pragma once
 
 #include "common.h"
+#include "lane.h"
 
 namespace fia {
 namespace {
-
-typedef double d4_t __attribute__((ext_vector_type(4)));
 
 // C += A B on the f64 matrix cores; lane l supplies A[l&15][l>>4] and B[l>>4][l&15],
 // and holds C[(l>>4) + 4r][l&15] in register r.
@@ -17,11 +18,8 @@ __device__ __forceinline__ d4_t mfma4(double a, double b, d4_t c) {
   return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
 }
 
-__device__ __forceinline__ double wsum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
+constexpr int kBigSlice = 2048;     // ratings per Gram work item (big_work_lists, k_big_gram)
+constexpr int kBigMfmaQB = 32;      // queries per scoring work item (build_groups, k_big_score_mfma)
 
 // ------------------------------------------------------------------------------------
 // model traits.  A side block has Ds coordinates padded to NPs = 16 T.
@@ -49,6 +47,15 @@ struct BNCF {
   // reference theta order [Pm_u, Qm_i, Pg_u, Qg_i]
   __device__ static int ref_index(int side, int a) { return a < K ? side * K + a : 2 * K + side * K + (a - K); }
 };
+
+// f(M{}) for the traits M of (model, k), its result returned; hipErrorInvalidValue for a size
+// that is not built
+template <class F>
+hipError_t big_dispatch(int model, int k, F&& f) {
+  hipError_t e = hipErrorInvalidValue;
+  for_big_size<BMF, BNCF>(model, k, [&](auto m) { e = f(m); });
+  return e;
+}
 
 // Gram tile storage: tile (tr, tc), tc <= tr, in column-major tile order; inside a tile
 // element (row m, col n) at m + 16 n.
@@ -138,26 +145,20 @@ constexpr size_t solve_lds() {
   return (size_t)((NP + 16) * (solve_nb<NP>() + 1) + NP + solve_nb<NP>() * solve_nb<NP>() + 64) * 8;
 }
 
-__device__ __forceinline__ double readlane_dbl(double v, int l) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
+// block-wide sum for workgroups of NW waves (every thread gets the result; red: NW doubles)
 template <int NW>
 __device__ __forceinline__ double bsum(double x, double* red) {
-  x = wsum(x);
+  x = wave_sum(x);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = x;
   __syncthreads();
-  double t = 0.0;
+  double t = red[0];
 #pragma unroll
-  for (int w = 0; w < NW; ++w) t += red[w];
+  for (int w = 1; w < NW; ++w) t += red[w];
   return t;
 }
 
-// P: LDR * (NB + 1) doubles, dd: NP, W11: NB * NB (all LDS).  k_big_solve (bigk.hip) keeps
+// P: LDR * (NB + 1) doubles, dd: NP, W11: NB * NB (all LDS).  k_big_solve (bigk_solve.hip) keeps
 // this loop in its own body (see there: through this function its MF k = 256 instantiation
 // spilled twice the registers); a change to one belongs in the other.
 template <int NP, class AOrig>
@@ -229,10 +230,10 @@ __device__ __forceinline__ void big_ldlt_solve(const AOrig& aorig, double* Ls, d
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
         // entries right of a lane's diagonal become garbage and are never read
-        const double dj = readlane_dbl(a[j], j);
+        const double dj = readlane_d(a[j], j);
         const double f = lane > j ? a[j] / dj : 0.0;   // lane r > j: L[r][j]
 #pragma unroll
-        for (int t = j + 1; t < NB; ++t) a[t] = fma(-f, readlane_dbl(a[j], t), a[t]);
+        for (int t = j + 1; t < NB; ++t) a[t] = fma(-f, readlane_d(a[j], t), a[t]);
       }
       double dl = a[0];
 #pragma unroll
@@ -247,7 +248,7 @@ __device__ __forceinline__ void big_ldlt_solve(const AOrig& aorig, double* Ls, d
       // L of the block (rows c0 + r > c0 + t): a[t] / d_t
 #pragma unroll
       for (int t = 0; t < NB; ++t) {
-        const double dt = readlane_dbl(dl, t);
+        const double dt = readlane_d(dl, t);
         if (lane < nbe && t < lane) Ls[(int64_t)(c0 + t) * LDR + c0 + lane] = a[t] / dt;
       }
     }
@@ -296,7 +297,7 @@ __device__ __forceinline__ void big_ldlt_solve(const AOrig& aorig, double* Ls, d
       double val = lane < bw ? xs[b0 + lane] : 0.0;
       const double* __restrict__ Wc = W11 + (lane < BW ? lane : 0) * BW;
       for (int t = bw - 1; t >= 0; --t) {
-        const double xt = readlane_dbl(val, t);
+        const double xt = readlane_d(val, t);
         if (lane < t) val = fma(-Wc[t], xt, val);
       }
       if (lane < bw) xs[b0 + lane] = val;
@@ -317,4 +318,32 @@ __device__ __forceinline__ void big_ldlt_solve(const AOrig& aorig, double* Ls, d
 }
 
 }  // namespace
+
+// ---- launchers of the kernel units, for the host side (bigk.hip).  (model, k) is a size of
+// FIA_BIG_SIZES (else hipErrorInvalidValue); the buffers of the context are reserved by the
+// caller; the batch's BigArgs are made from (c, qu, qi) ----
+// bigk_prepare.hip
+hipError_t launch_self(int64_t N, int64_t n_ent, const int64_t* ptr, int32_t* self, hipStream_t s);
+hipError_t launch_check_cover(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, int32_t* flag,
+                              hipStream_t s);
+// per train row: the residual and (NCF) the layer-1 rows, weight fragments and g_mlp of both
+// sides; marked: only the rows that the entities of c->mark read
+hipError_t launch_big_rows(int model, int k, fia_ctx* c, bool marked, hipStream_t s);
+// the Gram caches of side sd from its work lists (big_work_lists), split lists summed
+hipError_t launch_big_gram(int model, int k, fia_ctx* c, int sd, hipStream_t s);
+// bigk_solve.hip: the per-query work words and solve lists; the coupled systems of c->cpllist,
+// one workgroup each; the records from a given x; the record headers and x_out
+hipError_t launch_big_prologue(int model, int k, fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi,
+                               hipStream_t s);
+hipError_t launch_solve(int model, int k, fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, hipStream_t s);
+hipError_t launch_big_record_x(int model, int k, fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi,
+                               const double* x_in, hipStream_t s);
+hipError_t launch_big_finish(int model, int k, fia_ctx* c, int64_t Q, double* x_out, hipStream_t s);
+// bigk_solve_batched.hip: the side systems of c->syslist through the batched panel kernels
+hipError_t launch_solve_batched(int model, int k, fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi,
+                                hipStream_t s);
+// bigk_score.hip: the work items of build_groups, timed by the dispatch itself (ps)
+hipError_t launch_big_score(int model, int k, fia_ctx* c, const int32_t* qu, const int32_t* qi, int64_t max_chunks,
+                            int32_t* rel_idx, double* influence, int K, PhaseSpan ps, hipStream_t s);
+
 }  // namespace fia

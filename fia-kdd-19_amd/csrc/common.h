@@ -139,11 +139,11 @@ struct Index {
 // ---- the (model, k) sizes the library is built for, each spelled once ----
 // small k: every structure of a query fits a wave's registers or a workgroup's LDS (models.hip)
 #define FIA_SMALL_SIZES(X) X(MF, 8) X(MF, 16) X(MF, 32) X(MF, 64) X(NCF, 8) X(NCF, 16) X(NCF, 32)
-// large k (bigk.hip)
+// large k (bigk.hip and the bigk_*.hip kernel units)
 #define FIA_BIG_SIZES(X) X(MF, 128) X(MF, 256) X(NCF, 64) X(NCF, 128) X(NCF, 256)
 
 // f(MF<k>{}) or f(NCF<k>{}) for the size (model, k) of a list, MF / NCF being the caller's trait
-// templates (MFm / NCFm of kern.h, BMF / BNCF of bigk.hip); false, and f not called, for a size
+// templates (MFm / NCFm of kern.h, BMF / BNCF of bigk.h); false, and f not called, for a size
 // not in the list.  f's own result goes out through its captures.
 #define FIA_SIZE_CASE(fam, kv)                \
   if (model == FIA_MODEL_##fam && k == kv) {  \
@@ -331,7 +331,7 @@ namespace fia {
 // What every kernel reads of the model: the table sizes, the list pointers, the parameter tables,
 // the dense NCF layer-1 rows and the weight decay.  The argument structs of the kernels that read
 // nothing else of the context (score_cand.hip, total.hip) derive from it; QueryArgs (kern.h) and
-// BigArgs (bigk.hip) hold the same members among their own, in the order their kernels were
+// BigArgs (bigk.h) hold the same members among their own, in the order their kernels were
 // tuned with (moving them changed the register counts of three solve kernels).
 struct ModelArgs {
   int64_t U, I;
@@ -405,6 +405,8 @@ hipError_t join_l1(fia_ctx* c, hipStream_t s);
 // their Gram caches on ps
 hipError_t prepare_model_for(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, hipStream_t s, hipStream_t ps,
                              bool& unsupported, bool mark_only);
+// c->mark: 1 for every user u and item U + i of the Q queries (out-of-range queries skipped)
+hipError_t mark_entities(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, hipStream_t s);
 hipError_t check_cover_small(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, int32_t* flag,
                              hipStream_t s);
 hipError_t query_model(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* offsets,

@@ -1,12 +1,14 @@
-// Definitions shared by every translation unit but index.hip, bigk.hip and abi.hip: the model
-// traits and the dispatch from (model, k) to them, top-K order helpers and selections,
-// wave-level reductions, and the per-batch kernel arguments.  gfx950 only.
+// Definitions shared by the small-k translation units: the model traits and the dispatch from
+// (model, k) to them, the top-K selections and the per-batch kernel arguments.  The lane
+// helpers they build on (wave reductions, the top-K order) are in lane.h, which the large-k
+// units share.  gfx950 only.
 #pragma once
 
 #include <cmath>
 #include <cstdint>
 
 #include "common.h"
+#include "lane.h"
 
 namespace fia {
 
@@ -79,23 +81,6 @@ constexpr bool pair_layout() { return M::ncf && M::Ds == 32; }
 template <class M>
 constexpr bool mask_path() { return M::ncf && M::K <= 16; }
 
-// 4 doubles per lane: an f64 MFMA 16x16 tile (C/D layout: element (4 r + (l >> 4), l & 15) in [r])
-typedef double d4_t __attribute__((ext_vector_type(4)));
-
-// lane l's double, broadcast to the wave (v_readlane into SGPRs; l compile-time)
-__device__ __forceinline__ double readlane_d(double v, int l) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), l);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
-}
-
-__device__ __forceinline__ double wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
-  return x;
-}
-
 template <int N>
 __device__ __forceinline__ void load_row_f32(const float* __restrict__ src, double* dst) {
   if constexpr (N % 4 == 0) {
@@ -111,85 +96,6 @@ __device__ __forceinline__ void load_row_f32(const float* __restrict__ src, doub
   } else {
 #pragma unroll
     for (int c = 0; c < N; ++c) dst[c] = src[c];
-  }
-}
-
-// ------------------------------------------------------------------------------------
-// top-K helpers: order = |v| descending, then related position ascending
-// ------------------------------------------------------------------------------------
-__device__ __forceinline__ double topk_key(double v) {
-  double a = fabs(v);
-  return (a != a) ? -1.0 : a;     // NaN ranks last among real candidates
-}
-__device__ __forceinline__ bool better(double a1, int p1, double a2, int p2) {
-  return a1 > a2 || (a1 == a2 && p1 < p2);
-}
-
-// The best (key, position, value) of the wave, in every lane.  `better` is a strict total
-// order on (key, position) -- positions are unique, invalid lanes all carry the same
-// (-2, INT_MAX, 0) -- so the result does not depend on the reduction order: DPP row
-// rotations inside each 16-lane row, then permlane swaps across the rows (all VALU; the
-// ds_bpermute butterfly it replaces waited an LDS round trip per level, six per call)
-template <int CTRL>
-__device__ __forceinline__ int dpp_i32(int x) {
-  // old = x: a disabled source lane returns the lane's own value (a no-op merge)
-  return __builtin_amdgcn_update_dpp(x, x, CTRL, 0xf, 0xf, false);
-}
-__device__ __forceinline__ void best_take(double& a, int& p, double& v, double oa, int op, double ov) {
-  if (better(oa, op, a, p)) { a = oa; p = op; v = ov; }
-}
-template <int CTRL>
-__device__ __forceinline__ void best_dpp_step(double& a, int& p, double& v) {
-  const long long ab = __double_as_longlong(a), vb = __double_as_longlong(v);
-  const int alo = dpp_i32<CTRL>((int)(ab & 0xffffffffll)), ahi = dpp_i32<CTRL>((int)(ab >> 32));
-  const int vlo = dpp_i32<CTRL>((int)(vb & 0xffffffffll)), vhi = dpp_i32<CTRL>((int)(vb >> 32));
-  const int op = dpp_i32<CTRL>(p);
-  best_take(a, p, v, __longlong_as_double(((long long)ahi << 32) | (unsigned)alo), op,
-            __longlong_as_double(((long long)vhi << 32) | (unsigned)vlo));
-}
-// the other row of the lane's pair: rows 0<->1, 2<->3 (SW32 = false) or 0,1<->2,3 (SW32 = true)
-template <bool SW32>
-__device__ __forceinline__ unsigned other_rows(unsigned x) {
-  const bool up = SW32 ? (threadIdx.x & 32) != 0 : (threadIdx.x & 16) != 0;
-  if constexpr (SW32) {
-    const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);   // {[r0 r1 r0 r1], [r2 r3 r2 r3]}
-    return up ? r[0] : r[1];
-  } else {
-    const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);   // {[r0 r0 r2 r2], [r1 r1 r3 r3]}
-    return up ? r[0] : r[1];
-  }
-}
-template <bool SW32>
-__device__ __forceinline__ void best_row_step(double& a, int& p, double& v) {
-  const long long ab = __double_as_longlong(a), vb = __double_as_longlong(v);
-  const unsigned alo = other_rows<SW32>((unsigned)(ab & 0xffffffffll)), ahi = other_rows<SW32>((unsigned)(ab >> 32));
-  const unsigned vlo = other_rows<SW32>((unsigned)(vb & 0xffffffffll)), vhi = other_rows<SW32>((unsigned)(vb >> 32));
-  const int op = (int)other_rows<SW32>((unsigned)p);
-  best_take(a, p, v, __longlong_as_double(((long long)ahi << 32) | alo), op,
-            __longlong_as_double(((long long)vhi << 32) | vlo));
-}
-__device__ __forceinline__ void wave_best(double& a, int& p, double& v) {
-  best_dpp_step<0x128>(a, p, v);   // row_ror:8
-  best_dpp_step<0x124>(a, p, v);   // row_ror:4
-  best_dpp_step<0x122>(a, p, v);   // row_ror:2
-  best_dpp_step<0x121>(a, p, v);   // row_ror:1 -- every lane of a row holds the row's best
-  best_row_step<false>(a, p, v);
-  best_row_step<true>(a, p, v);
-}
-
-// The best (key, position, value) of a workgroup of NW waves, in every thread (s_*: NW entries)
-template <int NW>
-__device__ __forceinline__ void block_best(double& ba, int& bp, double& bv, double* s_a, int* s_p, double* s_v) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  wave_best(ba, bp, bv);
-  if (NW > 1) {
-    if (lane == 0) { s_a[wave] = ba; s_p[wave] = bp; s_v[wave] = bv; }
-    __syncthreads();
-    ba = s_a[0]; bp = s_p[0]; bv = s_v[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w)
-      if (better(s_a[w], s_p[w], ba, bp)) { ba = s_a[w]; bp = s_p[w]; bv = s_v[w]; }
-    __syncthreads();
   }
 }
 
@@ -316,13 +222,6 @@ __device__ void load_ncf_weights(NCFWeights<K>& w, const float* W2, const float*
   for (int t = threadIdx.x; t < K * H; t += blockDim.x) w.W2[t] = W2[t];
   for (int t = threadIdx.x; t < H; t += blockDim.x) w.b2[t] = b2[t];
   for (int t = threadIdx.x; t < 3 * H; t += blockDim.x) w.W3[t] = W3[t];
-}
-
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 struct QueryArgs {

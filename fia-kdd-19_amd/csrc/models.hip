@@ -3109,11 +3109,12 @@ hipError_t prepare_model(fia_ctx* c, hipStream_t s, bool& unsupported) {
   return hipSuccess;
 }
 
-// fia_prepare_for, small k: the queries' users and items are marked on the device (no host
-// round trip) and only their Gram caches (NCF: and per-position rows) are built; the cover
-// check of later fia_count_related calls reads the same marks
-__global__ void k_mark_small(int64_t Q, const int32_t* __restrict__ qu, const int32_t* __restrict__ qi, int64_t U,
-                             int64_t I, uint8_t* __restrict__ mark) {
+// fia_prepare_for: the entities referenced by a query set, users [0, U) and items [U, U + I) of
+// c->mark.  Small k builds only their Gram caches (NCF: and per-position rows) from the marks on
+// the device (no host round trip), and the cover check of later fia_count_related calls reads
+// the same marks; large k (bigk.hip) numbers its cache slots from them on the host.
+__global__ void k_mark(int64_t Q, const int32_t* __restrict__ qu, const int32_t* __restrict__ qi, int64_t U,
+                       int64_t I, uint8_t* __restrict__ mark) {
   for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < Q; q += (int64_t)gridDim.x * blockDim.x) {
     const int32_t u = qu[q], i = qi[q];
     if (u >= 0 && u < U && i >= 0 && i < I) {
@@ -3121,6 +3122,19 @@ __global__ void k_mark_small(int64_t Q, const int32_t* __restrict__ qu, const in
       mark[U + i] = 1;
     }
   }
+}
+
+hipError_t mark_entities(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, hipStream_t s) {
+  const int64_t U = c->p.U, I = c->p.I;
+  FIA_HIP_TRY(c->mark.reserve((size_t)(U + I), s));
+  FIA_HIP_TRY(hipMemsetAsync(c->mark.ptr, 0, (size_t)(U + I), s));
+  if (Q > 0) {
+    const int64_t gq = (Q + 255) / 256;
+    hipLaunchKernelGGL(k_mark, dim3((unsigned)(gq < 4096 ? gq : 4096)), dim3(256), 0, s, Q, qu, qi, U, I,
+                       c->mark.as<uint8_t>());
+    FIA_HIP_TRY(hipGetLastError());
+  }
+  return hipSuccess;
 }
 
 __global__ void k_check_mark(int64_t Q, const int32_t* __restrict__ qu, const int32_t* __restrict__ qi, int64_t U,
@@ -3136,16 +3150,8 @@ __global__ void k_check_mark(int64_t Q, const int32_t* __restrict__ qu, const in
 hipError_t prepare_model_for(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, hipStream_t s, hipStream_t ps,
                              bool& unsupported, bool mark_only) {
   unsupported = false;
-  const int64_t U = c->p.U, I = c->p.I;
   if (mark_only) {
-    FIA_HIP_TRY(c->mark.reserve((size_t)(U + I), s));
-    FIA_HIP_TRY(hipMemsetAsync(c->mark.ptr, 0, (size_t)(U + I), s));
-    if (Q > 0) {
-      const int64_t gq = (Q + 255) / 256;
-      hipLaunchKernelGGL(k_mark_small, dim3((unsigned)(gq < 4096 ? gq : 4096)), dim3(256), 0, s, Q, qu, qi, U, I,
-                         c->mark.as<uint8_t>());
-      FIA_HIP_TRY(hipGetLastError());
-    }
+    FIA_HIP_TRY(mark_entities(c, Q, qu, qi, s));
     c->subset = false;
     c->small_subset = false;
     return hipSuccess;

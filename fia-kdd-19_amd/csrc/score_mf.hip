@@ -11,57 +11,6 @@ namespace fia {
 constexpr int kRunsWaves = 3;   // waves per SIMD the register budget is sized for
 namespace {
 
-// The wave's best (key, position, value) under the strict (key desc, position asc) order,
-// in every lane: the wave max of the keys, then the smallest position among the lanes
-// holding it (positions are unique among valid candidates, invalid lanes carry (-2,
-// INT_MAX)), then that lane's value.  The same winner as wave_best with a third of the VALU
-// (one f64 max and one i32 min per step instead of a full compare-and-select of the triple).
-template <int CTRL>
-__device__ __forceinline__ double dpp_max_f64(double m) {
-  const long long b = __double_as_longlong(m);
-  const int lo = dpp_i32<CTRL>((int)(b & 0xffffffffll)), hi = dpp_i32<CTRL>((int)(b >> 32));
-  return fmax(m, __longlong_as_double(((long long)hi << 32) | (unsigned)lo));
-}
-template <bool SW32>
-__device__ __forceinline__ double rows_max_f64(double m) {
-  const long long b = __double_as_longlong(m);
-  const unsigned lo = other_rows<SW32>((unsigned)(b & 0xffffffffll)), hi = other_rows<SW32>((unsigned)(b >> 32));
-  return fmax(m, __longlong_as_double(((long long)hi << 32) | lo));
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_min_i32(int p) {
-  const int o = dpp_i32<CTRL>(p);
-  return o < p ? o : p;
-}
-__device__ __forceinline__ void wave_top1(double& a, int& p, double& v) {
-  double m = dpp_max_f64<0x128>(a);
-  m = dpp_max_f64<0x124>(m);
-  m = dpp_max_f64<0x122>(m);
-  m = dpp_max_f64<0x121>(m);
-  m = rows_max_f64<false>(m);
-  m = rows_max_f64<true>(m);
-  int pc = a == m ? p : 0x7fffffff;
-  pc = dpp_min_i32<0x128>(pc);
-  pc = dpp_min_i32<0x124>(pc);
-  pc = dpp_min_i32<0x122>(pc);
-  pc = dpp_min_i32<0x121>(pc);
-  {
-    const int o = (int)other_rows<false>((unsigned)pc);
-    pc = o < pc ? o : pc;
-  }
-  {
-    const int o = (int)other_rows<true>((unsigned)pc);
-    pc = o < pc ? o : pc;
-  }
-  const unsigned long long who = __ballot(a == m && p == pc);
-  const int l = who ? (int)__builtin_ctzll(who) : 0;
-  const long long vb = __double_as_longlong(v);
-  const int vlo = __builtin_amdgcn_readlane((int)(vb & 0xffffffffll), l), vhi = __builtin_amdgcn_readlane((int)(vb >> 32), l);
-  v = __longlong_as_double(((long long)vhi << 32) | (unsigned)vlo);
-  a = m;
-  p = pc;
-}
-
 // k_score_mf_runs (MF k <= 16, the headline kernel).  A work descriptor is one chunk
 // (<= kRunChunk = 128 consecutive ratings) of ONE side's list together with a RUN of
 // consecutive batch queries sharing that side's entity (build_chunks runs mode: an item-side

@@ -1,5 +1,5 @@
 """Tabulate hipcc -Rpass-analysis=kernel-resource-usage remarks: one line per kernel.
-usage: python tools/resusage.py fia-kdd-19_amd/csrc/bigk.hip [filter]"""
+usage: python tools/resusage.py fia-kdd-19_amd/csrc/bigk_solve.hip [filter]"""
 import re
 import subprocess
 import sys
