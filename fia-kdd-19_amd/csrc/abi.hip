@@ -650,6 +650,34 @@ int fia_self_influence(fia_ctx* c, int64_t num_rows, const int32_t* rows, double
   })
 }
 
+int fia_query_batch_newton(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* offsets,
+                           int64_t total_rel, int32_t* rel_idx, double* newton, int K, int64_t* topk_pos,
+                           int64_t* topk_idx, double* topk_val, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
+    if (Q < 0 || Q >= (1LL << 31)) return fail(c, FIA_ERR_INVALID, "num_queries out of range");
+    if (total_rel < 0) return fail(c, FIA_ERR_INVALID, "total_rel < 0");
+    if (K < 0 || K > FIA_MAX_TOPK) return fail(c, FIA_ERR_INVALID, "K must be in [0, FIA_MAX_TOPK]");
+    if (Q > 0 && (!qu || !qi || !offsets)) return fail(c, FIA_ERR_INVALID, "null query array");
+    if (K > 0 && (!topk_pos || !topk_idx || !topk_val)) return fail(c, FIA_ERR_INVALID, "null top-K output");
+    if (Q == 0) return FIA_OK;
+    if (!fia::newton_supported(c->p.model, c->p.k))
+      return fail(c, FIA_ERR_UNSUPPORTED,
+                  "fia_query_batch_newton is built for MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32}; the large-k "
+                  "models are not supported yet");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_query_batch_newton"); rc != FIA_OK) return rc;
+    // the Gram caches of a pending small-k pass are read: join it, as fia_group_influence does
+    if (hipError_t es = fia::join_prepare(c, s); es != hipSuccess) return hip_fail(c, es, "fia_query_batch_newton");
+    hipError_t e = fia::query_newton(c, Q, qu, qi, offsets, total_rel, rel_idx, newton, K, topk_pos, topk_idx,
+                                     topk_val, s);
+    if (e != hipSuccess) return hip_fail(c, e, "fia_query_batch_newton");
+    return FIA_OK;
+  })
+}
+
 int fia_set_profiling(fia_ctx* c, int phase_mask) {
   if (!c) return FIA_ERR_INVALID;
   c->profiling = (unsigned)phase_mask & ((1u << FIA_NUM_PHASES) - 1u);

@@ -518,6 +518,16 @@ hipError_t self_influence(fia_ctx* c, int64_t n, const int32_t* rows, double* fi
                           double* error, int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val,
                           hipStream_t s);
 
+// fia_query_batch_newton (newton.hip): the Newton-corrected influence of every related rating,
+// one factorisation per query and a quadratic form per rating; the small-k sizes
+// (newton_supported); scratch: c->rec (the per-query records, in launches of bounded size),
+// c->coff, c->cdesc, c->cand_pos, c->cand_val, c->d1tab, and c->gxq for the own-pair values
+// when `newton` is NULL
+bool newton_supported(int model, int k);
+hipError_t query_newton(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* offsets,
+                        int64_t total_rel, int32_t* rel_idx, double* newton, int K, int64_t* topk_pos,
+                        int64_t* topk_idx, double* topk_val, hipStream_t s);
+
 // phase event helpers (no-ops unless profiling)
 void phase_begin(fia_ctx* c, int phase, hipStream_t s);
 void phase_end(fia_ctx* c, int phase, hipStream_t s);

@@ -42,6 +42,7 @@ SIGNATURES = {
     "fia_total_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P]),
     "fia_group_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
     "fia_self_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
+    "fia_query_batch_newton": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
     "fia_num_params": (ctypes.c_int, [_P]),
     "fia_set_profiling": (ctypes.c_int, [_P, ctypes.c_int]),
     "fia_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I64)]),
@@ -350,6 +351,42 @@ class Context(object):
         rc = self.lib.fia_self_influence(self.h, n, _ptr(rows), _ptr(first_order), _ptr(newton), _ptr(error), int(K),
                                          _ptr(topk_pos), _ptr(topk_idx), _ptr(topk_val), _stream())
         self._check(rc, "fia_self_influence")
+
+    def query_batch_newton(self, qu, qi, offsets, total, rel_idx=None, newton=None, K=0, topk_pos=None,
+                           topk_idx=None, topk_val=None):
+        """fia_query_batch_newton: for every related rating of every query its Newton-corrected
+        influence -- the system without that rating's curvature, one factorisation per query --
+        into newton (float64 [total]), the train rows into rel_idx (int32 [total]), and with K the
+        K related ratings of largest |newton| per query (topk_pos / topk_idx int64 [Q * K],
+        topk_val float64 [Q * K]).  offsets / total as count_related returns them."""
+        import torch
+        for t, name in ((qu, "qu"), (qi, "qi"), (rel_idx, "rel_idx")):
+            self._need_int32(t, name)
+        if qi.numel() != qu.numel():
+            raise ValueError("qu and qi must have the same length")
+        Q = qu.numel()
+        if offsets.dtype != torch.int64 or offsets.numel() != Q + 1:
+            raise TypeError("offsets must be a torch.int64 tensor of Q + 1 values")
+        for t, name in ((newton, "newton"), (topk_val, "topk_val")):
+            if t is not None and t.dtype != torch.float64:
+                raise TypeError("%s must be a torch.float64 tensor" % name)
+        for t, name in ((topk_pos, "topk_pos"), (topk_idx, "topk_idx")):
+            if t is not None and t.dtype != torch.int64:
+                raise TypeError("%s must be a torch.int64 tensor" % name)
+        for t, name in ((qu, "qu"), (qi, "qi"), (offsets, "offsets"), (rel_idx, "rel_idx"), (newton, "newton"),
+                        (topk_pos, "topk_pos"), (topk_idx, "topk_idx"), (topk_val, "topk_val")):
+            if t is not None and not (t.is_cuda and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous device (cuda) tensor" % name)
+        for t, name in ((rel_idx, "rel_idx"), (newton, "newton")):
+            if t is not None and t.numel() < total:
+                raise ValueError("%s holds %d values, the batch has %d related ratings" % (name, t.numel(), total))
+        if K and (topk_pos is None or topk_idx is None or topk_val is None
+                  or min(topk_pos.numel(), topk_idx.numel(), topk_val.numel()) < Q * K):
+            raise ValueError("top-K outputs must hold Q * K values")
+        rc = self.lib.fia_query_batch_newton(self.h, Q, _ptr(qu), _ptr(qi), _ptr(offsets), int(total), _ptr(rel_idx),
+                                             _ptr(newton), int(K), _ptr(topk_pos), _ptr(topk_idx), _ptr(topk_val),
+                                             _stream())
+        self._check(rc, "fia_query_batch_newton")
 
     # ---- profiling ----
     def set_profiling(self, on, phases=None):

@@ -665,6 +665,55 @@ class GenericNeuralNet(object):
             out["topk_val"] = tv[:K].cpu().numpy()
         return out
 
+    def get_newton_influence_batch(self, test_indices, K=1, full=True):
+        """Newton-corrected influence of EVERY related rating of many test ratings (one
+        fia_query_batch_newton call): per related position p of test rating q, with train row j,
+
+            newton[offsets[q] + p] = v . (H - H_j)^-1 b_j
+
+        -- get_influence_batch's influence with the rating's own curvature taken out of the system
+        (get_group_influence of the single group {j}; include/fia.h), from one factorisation per
+        query.  A train row that is the test pair itself holds the same value at both of its
+        positions.  test_indices must be a 1-d sequence of integers, K in [0, FIA_MAX_TOPK];
+        these, and full=False with K == 0, are checked on the host (ValueError) before any GPU
+        call.  Returns numpy arrays shaped as get_influence_batch's: offsets int64 [Q + 1]; with
+        full rel_idx int64 and newton float64 [total]; with K topk_pos, topk_idx int64 [Q, K] and
+        topk_val float64 [Q, K] by |newton| (ties to the lower position, -1 / NaN in unused slots)."""
+        if isinstance(K, bool) or int(K) != K or not 0 <= int(K) <= _lib.FIA_MAX_TOPK:
+            raise ValueError("K must be in [0, %d]" % _lib.FIA_MAX_TOPK)
+        K = int(K)
+        if not full and K == 0:
+            raise ValueError("nothing to return: full=False needs K > 0")
+        t = np.asarray(test_indices)
+        if t.size == 0:
+            t = np.zeros(0, np.int64)
+        if t.ndim != 1:
+            raise ValueError("test_indices must be a 1-d sequence of test rows")
+        if t.dtype.kind not in "iu":
+            raise ValueError("test rows must be integers (got dtype %s)" % t.dtype)
+        if t.size and t.min() < 0:
+            raise ValueError("test rows must be >= 0")
+        import torch
+        qu, qi = self._query_tensors([int(v) for v in t])
+        Q = qu.numel()
+        dev = self.ctx.torch_device
+        offsets, total = self.ctx.count_related(qu, qi)
+        rel = torch.empty(max(total, 1), dtype=torch.int32, device=dev) if full else None
+        nw = torch.empty(max(total, 1), dtype=torch.float64, device=dev) if full else None
+        tp = torch.empty(max(Q * K, 1), dtype=torch.int64, device=dev) if K else None
+        ti = torch.empty(max(Q * K, 1), dtype=torch.int64, device=dev) if K else None
+        tv = torch.empty(max(Q * K, 1), dtype=torch.float64, device=dev) if K else None
+        self.ctx.query_batch_newton(qu, qi, offsets, total, rel, nw, K, tp, ti, tv)
+        out = dict(offsets=offsets.cpu().numpy())
+        if full:
+            out["rel_idx"] = rel[:total].cpu().numpy().astype(np.int64)
+            out["newton"] = nw[:total].cpu().numpy()
+        if K:
+            out["topk_pos"] = tp[:Q * K].cpu().numpy().reshape(Q, K)
+            out["topk_idx"] = ti[:Q * K].cpu().numpy().reshape(Q, K)
+            out["topk_val"] = tv[:Q * K].cpu().numpy().reshape(Q, K)
+        return out
+
     def _predict_device(self, qu, qi):
         """r-hat(u, i) in fp64 on the device from the uploaded (float32) parameter tables."""
         import torch

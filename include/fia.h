@@ -342,6 +342,57 @@ int fia_group_influence(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user
                         double* dtheta,              /* device [G*D], reference theta order, nullable  */
                         void* stream);
 
+/* Newton-corrected influence of EVERY related rating of a batch of test predictions: what
+ * fia_query_batch scores to first order -- each rating against the Hessian of the full related
+ * list -- with the rating's own curvature taken out of the system.  H is a mean over only n_q
+ * ratings; for a user with a few dozen ratings one rating is a few percent of it, and the
+ * corrected and first-order values can differ by the size of the value itself.
+ * Query q = (u, i), n = n_q.  Related position p holds train row j = rel[p] = (a, b, y), with m_j,
+ * g_j, e_j, H_S, b_S, C and M as in fia_group_influence:
+ *   newton[offsets[q] + p] = v . (H - H_{j})^-1 b_{j}
+ * exactly the `group` output of fia_group_influence for query q and the group {j}.  A row that is
+ * the query's own pair sits in the list twice (m_j = 2): both positions hold the same value, the
+ * effect of removing that train row.  For m_j = 1 the first-order counterpart is fia_query_batch's
+ * influence[offsets[q] + p].
+ * Closed form for m_j = 1 (every row but the own pair; a == u and b == i together mean the own pair):
+ *   H'  = H - (wd/n) * diag(M)            the same for every rating of the query
+ *   c   = 2/n,  x' = H'^-1 v,  w' = H'^-1 (wd * M * theta_t) / n,  c' = x' . (wd * M * theta_t) / n
+ *   s_j = x' . g_j,  t_j = w' . g_j,  h_j = g_j^T H'^-1 g_j
+ *   newton_j = 2 e_j s_j / n + c' + c * s_j * (2 e_j h_j / n + t_j) / (1 - c * h_j)
+ * one factorisation per query and a quadratic form per rating (g_j is nonzero in one side's block:
+ * h_j needs that side's diagonal block of the FULL inverse H'^-1, coupled or not).  1 - c h_j can be
+ * small and, for a coupled query (H indefinite through 2 e C), negative: nothing assumes its sign; a
+ * zero denominator yields whatever the arithmetic yields (the system is singular there).  Own-pair
+ * rows (m_j = 2: coupling block, twice the decay share -- not rank one) get the full downdated
+ * solve of fia_self_influence's newton, one per such row, each with its own e_j.
+ * Arguments as fia_query_batch (offsets from fia_count_related, total_rel == offsets[Q]); rel_idx
+ * (int32 train rows, as fia_query_batch writes them) and newton may be NULL.  topk (K in
+ * [0, FIA_MAX_TOPK]; 0 = off): per query the K related ratings of largest |newton| in
+ * fia_query_batch's order (ties: lower related position first, NaN last) as related position
+ * (topk_pos), train row (topk_idx) and signed value (topk_val), device arrays [Q*K]; unused slots
+ * hold -1 / NaN.  A query with n_q = 0 writes nothing; a query id outside [0, num_users) x
+ * [0, num_items) is never used as an index and counts as n_q = 0, as in fia_query_batch.
+ * num_queries == 0 returns FIA_OK and launches nothing.
+ * Needs params, index and a prepare (else FIA_ERR_STATE).  After fia_prepare_for the QUERIES must be
+ * covered, and the results are bitwise those after fia_prepare.  Ordered on `stream`, no host
+ * synchronisation; it reads the entity Gram caches, so it joins a pending small-k Gram pass as
+ * fia_group_influence does.  No floating-point atomics: the same inputs give the same bits wherever
+ * the query sits in the batch.
+ * Scratch: 2 * Ds^2 + 4 * Ds + 4 doubles per query (Ds the side block, k + 1 or 2k: 68 KB at MF
+ * k=64), bounded at 1 GiB per launch: a longer batch runs in chunks of queries on `stream`, and the
+ * results do not depend on the chunking.  With newton NULL the own-pair values go to context scratch
+ * (total_rel doubles).  The environment variable FIA_NEWTON_CHUNK (a positive integer) lowers the
+ * chunk length to that many queries per launch: a testing knob; a larger value is ignored.
+ * Sizes: MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32}.  The large-k models (MF k in {128, 256},
+ * NCF k in {64, 128, 256}) return FIA_ERR_UNSUPPORTED.  fia_version stays 100: no existing
+ * signature, struct or constant changed. */
+int fia_query_batch_newton(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item,
+                           const int64_t* offsets, int64_t total_rel,
+                           int32_t* rel_idx,         /* device [total_rel], nullable */
+                           double* newton,           /* device [total_rel], nullable */
+                           int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val,   /* device [Q*K] */
+                           void* stream);
+
 /* Self-influence: the effect of a train rating on its OWN prediction (its leverage), for every
  * listed train row in one fused pass -- the scan that finds noisy or injected ratings, and what
  * turns a leave-one-out residual into a Cook's-distance style score.  The reference has no
