@@ -439,6 +439,7 @@ SCORING_KERNELS = [
     ("MF", 32, 2), ("MF", 64, 2),                            # k_score_grouped_mf
     ("NCF", 32, 1),                                          # k_score_ncf
     ("MF", 128, 1), ("NCF", 64, 1),                          # k_big_score_mfma
+    ("MF", 256, 1), ("NCF", 128, 0), ("NCF", 256, 1),
 ]
 GUARD = 64                       # sentinel elements on each side of an output (at least)
 REL_SENTINEL = -7

@@ -306,7 +306,7 @@ def test_large_k_matches_oracle(model, k, tmp_path):
 
 
 @pytest.mark.parametrize("model,k", [("MF", 128), ("NCF", 64), ("MF", 16), ("MF", 64), ("NCF", 16), ("NCF", 8),
-                                     ("MF", 32), ("NCF", 32)])
+                                     ("MF", 32), ("NCF", 32), ("NCF", 256)])
 def test_prepare_for_subset(model, k, tmp_path):
     """fia_prepare_for: caches for only the queried users/items give the same
     results as the full prepare (bitwise), and a query outside the set is rejected
