@@ -137,7 +137,8 @@ struct Index {
 };
 
 // ---- the (model, k) sizes the library is built for, each spelled once ----
-// small k: every structure of a query fits a wave's registers or a workgroup's LDS (models.hip)
+// small k: every structure of a query fits a wave's registers or a workgroup's LDS (models.hip
+// and the small_*.hip, score_*.hip and gram_mf.hip kernel units)
 #define FIA_SMALL_SIZES(X) X(MF, 8) X(MF, 16) X(MF, 32) X(MF, 64) X(NCF, 8) X(NCF, 16) X(NCF, 32)
 // large k (bigk.hip and the bigk_*.hip kernel units)
 #define FIA_BIG_SIZES(X) X(MF, 128) X(MF, 256) X(NCF, 64) X(NCF, 128) X(NCF, 256)
@@ -467,7 +468,7 @@ hipError_t launch_score_mf_mfma(int k, bool full, int64_t grid, hipStream_t s, P
                                 int64_t nE, const int64_t* wstart, const int32_t* witems, const int64_t* gstart,
                                 const int32_t* gq, const int64_t* qbase, const double* rec, int32_t* rel_idx,
                                 double* influence, int K, int32_t* cand_pos, double* cand_val);
-// per-query merge of chunk top-K candidates (models.hip); spc = candidate slot sets per chunk
+// per-query merge of chunk top-K candidates (small_score.hip); spc = candidate slot sets per chunk
 hipError_t launch_topk_merge(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, int K, int spc,
                              int64_t* topk_pos, int64_t* topk_idx, double* topk_val, hipStream_t s,
                              int64_t max_chunks);

@@ -81,6 +81,48 @@ constexpr bool pair_layout() { return M::ncf && M::Ds == 32; }
 template <class M>
 constexpr bool mask_path() { return M::ncf && M::K <= 16; }
 
+// ---- which side-system solve a model takes (kernels in small_solve.hip) ----
+// MF k = 16: a quad of lanes per side system (k_solve_quad); MF k = 8: a thread per system
+template <class M>
+constexpr bool use_quad_solve() {
+  return !M::ncf && M::K == 16;
+}
+template <class M>
+constexpr bool use_tps() {
+  return !M::ncf && M::Ds <= 17 && !use_quad_solve<M>();
+}
+
+// side systems on 16x16 tiles: NCF (Ds = 2k) and MF k >= 32 (k coordinates + the bias)
+template <class M>
+constexpr bool use_tile_solve() {
+  return !use_tps<M>() && !use_quad_solve<M>() && (M::ncf ? M::Ds : M::K) % 16 == 0 &&
+         (M::ncf ? M::Ds : M::K) <= 64;
+}
+
+// NCF k <= 16: both side blocks in one wave, a column per lane (k_solve_col)
+template <class M>
+constexpr bool use_col_solve() {
+  return M::ncf && 2 * M::Ds <= 64;
+}
+
+// one side-system solve per model: MF k = 16 k_solve_quad, MF k = 8 k_solve_tps, NCF k = 16
+// k_solve_rows, NCF k = 8 k_solve_col, MF k in {32, 64} and NCF k = 32 k_solve_tile
+template <class M>
+constexpr bool solve_covered() {
+  return use_quad_solve<M>() || use_tps<M>() || pair_layout<M>() || use_col_solve<M>() || use_tile_solve<M>();
+}
+
+// doubles per query that k_ncf_query_pro hands to k_solve_rows (NCF k = 16)
+template <class M>
+constexpr int qpro_stride() { return M::D + 4; }
+
+// queries per entity-shared work item: 16 for MF k >= 64, where a work item's gathered
+// rows (256 B each) are the dominant traffic and two query blocks would load them twice
+template <class M>
+constexpr int query_block() {
+  return (!M::ncf && M::K >= 64) ? 16 : kQueryBlock;
+}
+
 template <int N>
 __device__ __forceinline__ void load_row_f32(const float* __restrict__ src, double* dst) {
   if constexpr (N % 4 == 0) {
@@ -244,8 +286,36 @@ struct QueryArgs {
   int64_t N;
   const double* d1tab;   // NCF k <= 16: d1 table [2^(k/2)][k] (k_ncf_d1_table)
 };
-// the context's index, caches and parameters as the small-k kernels read them (models.hip;
-// d1tab is set by the queries that read it)
+// the context's index, caches and parameters as the small-k kernels read them (d1tab is set by
+// the queries that read it)
 QueryArgs make_args(fia_ctx* c, const int32_t* qu, const int32_t* qi);
+
+// ---- the small-k kernels behind prepare_impl / query_impl (models.hip) ----
+struct ScanArgs;   // scan.h
+// small_gram.hip: NCF layer-1 rows of side sd; the per-slice Gram pass of both sides (MF
+// k_gram_mf_mfma, NCF k_ncf_gram_rows, which picks its waves per CU); the split lists' sums
+hipError_t launch_ncf_l1(int k, const float* emb, const float* W1, int sd, int64_t n_ent, double* out, hipStream_t s);
+hipError_t launch_gram_slices(int model, int k, fia_ctx* c, const uint8_t* mark, hipStream_t s);
+hipError_t launch_gram_combine(fia_ctx* c, int64_t nc0, const int32_t* comb0, int64_t nc1, const int32_t* comb1,
+                               int GS, int GSP, const uint8_t* mark, hipStream_t s);
+// small_solve.hip: the model's side-system solve with its grid rule (MF k = 16: the launch that
+// also runs the scan S and the coupled solves, stamping ps; the others append to `coupled` for
+// launch_coupled_solve, whose dispatch stamps `end`); NCF k = 16's per-query prologue into
+// qpro [Q * qpro_stride]; the records of a given x
+hipError_t launch_side_solve(int model, int k, fia_ctx* c, const ScanArgs& S, const QueryArgs& A, int64_t Q,
+                             double* x_out, int32_t* coupled, hipStream_t s, PhaseSpan ps);
+hipError_t launch_coupled_solve(int model, int k, const QueryArgs& A, int64_t Q, double* rec, double* x_out,
+                                int32_t* coupled, hipStream_t s, hipEvent_t end);
+hipError_t launch_ncf_query_pro(int k, const QueryArgs& A, int64_t Q, double* qpro, hipStream_t s);
+hipError_t launch_record_x(int model, int k, const QueryArgs& A, int64_t Q, const double* x_in, double* rec,
+                           double* x_out, hipStream_t s);
+// small_score.hip: entity-shared scoring, MF k in {32, 64} (k_score_grouped_mf) and NCF k = 32
+// (k_score_ncf); NCF k <= 16, per batch: the d1 table [2^(k/2)][k] and the records' y
+hipError_t launch_score_grouped(int model, int k, int64_t grid, hipStream_t s, PhaseSpan ps, const QueryArgs& A,
+                                int64_t nE, const int64_t* wstart, const int32_t* witems, const int64_t* gstart,
+                                const int32_t* gq, const int64_t* qbase, const double* rec, int32_t* rel_idx,
+                                double* influence, int K, int32_t* cand_pos, double* cand_val);
+hipError_t launch_ncf_d1_table(int k, const float* W2, const float* W3, double* tab, hipStream_t s);
+hipError_t launch_ncf_rec_y(int k, int64_t Q, const float* W1, double* rec, hipStream_t s);
 
 }  // namespace fia

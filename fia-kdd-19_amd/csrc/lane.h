@@ -1,5 +1,5 @@
 // Lane-level device helpers shared by the small-k units (through kern.h) and the large-k units
-// (through bigk.h): wave reductions and broadcasts, and the top-K order.  Nothing here knows a
+// (through bigk.h): wave and DPP row reductions and broadcasts, and the top-K order.  Nothing here knows a
 // model, a size or a kernel argument struct, so an edit to those reaches no unit through this
 // header.  gfx950 only.
 #pragma once
@@ -24,6 +24,39 @@ __device__ __forceinline__ double wave_sum(double x) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off);
   return x;
+}
+
+// lane CTRL's double (a DPP control: quad_perm, row_mirror, ...); a disabled source lane gives 0
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double x) {
+  const long long b = __double_as_longlong(x);
+  const int lo = __builtin_amdgcn_update_dpp(0, (int)(b & 0xffffffffll), CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xf, 0xf, false);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
+}
+// sum over the 16 lanes of each row (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror,
+// row_mirror); every lane of the row gets the bit-identical sum
+__device__ __forceinline__ double row_sum16(double x) {
+  x += dpp_d<0xB1>(x);
+  x += dpp_d<0x4E>(x);
+  x += dpp_d<0x141>(x);
+  x += dpp_d<0x140>(x);
+  return x;
+}
+// sum over the 4 rows (lanes c, c+16, c+32, c+48); every lane gets the same sum
+__device__ __forceinline__ double col_sum4(double x) {
+  const long long b = __double_as_longlong(x);
+  const unsigned lo = (unsigned)(b & 0xffffffffll), hi = (unsigned)(b >> 32);
+  const auto l16 = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+  const auto h16 = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+  const double s = __longlong_as_double(((long long)h16[0] << 32) | l16[0]) +
+                   __longlong_as_double(((long long)h16[1] << 32) | l16[1]);   // rows 0+1 | 2+3
+  const long long bs = __double_as_longlong(s);
+  const unsigned slo = (unsigned)(bs & 0xffffffffll), shi = (unsigned)(bs >> 32);
+  const auto l32 = __builtin_amdgcn_permlane32_swap(slo, slo, false, false);
+  const auto h32 = __builtin_amdgcn_permlane32_swap(shi, shi, false, false);
+  return __longlong_as_double(((long long)h32[0] << 32) | l32[0]) +
+         __longlong_as_double(((long long)h32[1] << 32) | l32[1]);
 }
 
 // wave-local LDS hand-off: a wave's LDS operations complete in order; this only keeps

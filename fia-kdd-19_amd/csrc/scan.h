@@ -1,6 +1,6 @@
 // Device body of the single-pass per-query scans (decoupled look-back), shared by the thin
 // k_query_scan kernels of index.hip and the scan role of the fused scan + side-solve launch of
-// models.hip (the library is built without relocatable device code: a kernel that runs the
+// small_solve.hip (the library is built without relocatable device code: a kernel that runs the
 // scan beside other work has to see the body in its own translation unit).
 #pragma once
 
@@ -327,7 +327,7 @@ __device__ __forceinline__ void query_scan_body(
 }
 
 // The scan's launch arguments as a kernel that runs it beside other work carries them
-// (models.hip); filled by chunk_scan_args (index.hip) after the reserves.
+// (k_solve_quad, small_solve.hip); filled by chunk_scan_args (index.hip) after the reserves.
 struct ScanArgs {
   const int32_t* qu;
   const int32_t* qi;

@@ -1,4 +1,4 @@
-// Device code of the full-D per-query system, shared by models.hip (k_solve, k_record_x and
+// Device code of the full-D per-query system, shared by small_solve.hip (k_solve, k_record_x and
 // the side-system solves' prologue), group.hip (fia_group_influence) and self.hip
 // (fia_self_influence): the LDS LDL^T, the
 // query prologue (theta_t, v = d r-hat / d theta_t, r-hat of one pair), the assembly of the

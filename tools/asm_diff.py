@@ -1,0 +1,55 @@
+#!/usr/bin/env python3
+"""Compare the kernels of two sets of gfx950 assembly files (hipcc ... --cuda-device-only -S).
+
+    tools/asm_diff.py OLD.s[,OLD2.s...] NEW.s[,NEW2.s...]
+
+Per kernel, keyed by its demangled name: the instruction text from the kernel's label to its
+.amdhsa_kernel block (comments dropped, the function number of local labels normalised) and the
+.amdhsa_ resource lines.  Prints the kernels only one side has and the ones that differ; exit
+status 1 if any kernel present on both sides differs.
+"""
+import re
+import subprocess
+import sys
+
+
+def kernels(paths):
+    out = {}
+    for path in paths.split(","):
+        lines = open(path).read().split("\n")
+        names = [m.group(1) for l in lines if (m := re.match(r"\s*\.amdhsa_kernel (\S+)", l))]
+        plain = subprocess.run(["c++filt"] + names, capture_output=True, text=True, check=True).stdout.split("\n")
+        for name, key in zip(names, plain):
+            start = lines.index(next(l for l in lines if l.startswith(name + ":")))
+            desc = next(i for i in range(start, len(lines)) if lines[i].strip() == ".amdhsa_kernel " + name)
+            end = next(i for i in range(desc, len(lines)) if lines[i].strip() == ".end_amdhsa_kernel")
+            text = [re.sub(r"\.LBB\d+_", ".LBB_", l.split(";")[0].rstrip()) for l in lines[start + 1:desc]]
+            text = [l for l in text if l.strip() and not l.strip().startswith((".section", ".p2align"))]
+            out[key] = (text, [l.strip() for l in lines[desc + 1:end]])
+    return out
+
+
+def main():
+    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
+    for k in sorted(set(old) - set(new)):
+        print("only in old:", k)
+    for k in sorted(set(new) - set(old)):
+        print("only in new:", k)
+    both = sorted(set(old) & set(new))
+    bad = 0
+    for k in both:
+        (ot, orr), (nt, nr) = old[k], new[k]
+        if ot != nt or orr != nr:
+            bad += 1
+            print("DIFFERS:", k)
+            for a, b in zip(orr, nr):
+                if a != b:
+                    print("   ", a, "->", b)
+            if ot != nt:
+                print("    instruction text: %d -> %d lines" % (len(ot), len(nt)))
+    print("%d kernels on both sides, %d identical, %d differ" % (len(both), len(both) - bad, bad))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
