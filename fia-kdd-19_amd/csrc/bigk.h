@@ -22,17 +22,73 @@ constexpr int kBigSlice = 2048;     // ratings per Gram work item (big_work_list
 constexpr int kBigMfmaQB = 32;      // queries per scoring work item (build_groups, k_big_score_mfma)
 
 // ------------------------------------------------------------------------------------
+// The per-query blocks that the kernels of one phase leave for the next (offsets in doubles; a
+// kernel reads them through its traits, M::Rec and M::Work).
+// The scoring record (c->rec), written by the solves, headed by k_big_finish, read by
+// k_big_score_mfma: RecHead (common.h), the side solves' partial sums, then the block of the user
+// side (sd = 0) and of the item side (sd = 1).
+// ------------------------------------------------------------------------------------
+struct BigRecHead : RecHead {
+  // c_q and x . v of each side system; k_big_finish sums them into RecHead's c_q and x_v
+  static constexpr int cq_u = 4, xv_u = 5, cq_i = 6, xv_i = 7;
+  static constexpr int cq_of(int sd) { return cq_u + 2 * sd; }
+  static constexpr int xv_of(int sd) { return xv_u + 2 * sd; }
+  static constexpr int head = 8;
+};
+template <int K>
+struct BigRecMF : BigRecHead {
+  // side block, from side(R, sd)
+  static constexpr int x = 0;                   // [K] x at the embedding coordinates
+  static constexpr int x_bias = K;              // x at the bias coordinate
+  static constexpr int dup_other = K + 1;       // the test pair's other endpoint (an id, as a double)
+  static constexpr int SB = K + 2;
+  static constexpr int size = head + 2 * SB;
+  static_assert(x_bias == x + K, "the solves write x and x_bias as one run");
+  template <class T>
+  static constexpr T* side(T* R, int sd) { return R + head + sd * SB; }   // of the record at R
+};
+template <int K>
+struct BigRecNCF : BigRecHead {
+  // side block, from side(R, sd)
+  static constexpr int x_mlp = 0;               // [K] x at the MLP embedding
+  static constexpr int w3g_x_gmf = K;           // [K] W3g * x at the GMF embedding
+  static constexpr int dup_other = 2 * K;       // the test pair's other endpoint (an id, as a double)
+  static constexpr int SB = 2 * K + 1;
+  static constexpr int size = head + 2 * SB;
+  template <class T>
+  static constexpr T* side(T* R, int sd) { return R + head + sd * SB; }   // of the record at R
+};
+// The work words (c->qwork), written by k_big_prologue, read by the solves, k_big_finish and the
+// downdated solves of group_big.hip
+template <int NPs>
+struct BigWork {
+  static constexpr int n = 0;                   // related ratings; 0: none, ids out of range or not cached
+  static constexpr int cdup = 1;                // copies of the test pair among the train rows
+  static constexpr int esum = 2;                // cdup * r-hat - the sum of their ratings
+  static constexpr int rhat = 3;                // r-hat(u, i)
+  static constexpr int coupled = 4;             // 1: cdup > 0, the query is one full system
+  static constexpr int head = 8;
+  // v = d r-hat(u,i) / d theta_t and theta_t of side sd, NPs each (pads zero).  The two sides lie
+  // back to back: a coupled system reads v(qw, 0) and theta(qw, 0) as vectors of 2 NPs
+  template <class T>
+  static constexpr T* v(T* qw, int sd) { return qw + head + sd * NPs; }
+  template <class T>
+  static constexpr T* theta(T* qw, int sd) { return qw + head + 2 * NPs + sd * NPs; }
+  static constexpr int size = head + 4 * NPs;
+};
+
+// ------------------------------------------------------------------------------------
 // model traits.  A side block has Ds coordinates padded to NPs = 16 T.
-//   MF  side [emb (k), bias, 0 pad]  (mf:43-65)    record [x_emb (k), x_bias, dup_other]
-//   NCF side [mlp emb (k), gmf emb (k)] (ncf:49-64) record [x_mlp (k), W3g*x_gmf (k), dup_other]
-// per-query record: [1/n, c_q, x.v, r-hat(u,i), cq_u, xv_u, cq_i, xv_i, side 0, side 1]
-// per-query work:   [n, cdup, esum, r-hat, coupled, -, -, -, v_u, v_i, theta_u, theta_i]
+//   MF  side [emb (k), bias, 0 pad]  (mf:43-65)
+//   NCF side [mlp emb (k), gmf emb (k)] (ncf:49-64)
 // ------------------------------------------------------------------------------------
 template <int K_>
 struct BMF {
   static constexpr int K = K_, H = 1, Ds = K + 1, NPs = K + 16, T = NPs / 16;
   static constexpr bool ncf = false;
-  static constexpr int SB = K + 2, R = 8 + 2 * SB, QW = 8 + 4 * NPs;
+  using Rec = BigRecMF<K>;
+  using Work = BigWork<NPs>;
+  static constexpr int SB = Rec::SB, R = Rec::size, QW = Work::size;
   __host__ __device__ static constexpr bool decayed(int a) { return a < K; }
   // reference theta order [p_u, q_i, b_u, b_i]
   __device__ static int ref_index(int side, int a) { return a < K ? side * K + a : 2 * K + side; }
@@ -42,7 +98,9 @@ template <int K_>
 struct BNCF {
   static constexpr int K = K_, H = K / 2, Ds = 2 * K, NPs = 2 * K, T = NPs / 16;
   static constexpr bool ncf = true;
-  static constexpr int SB = 2 * K + 1, R = 8 + 2 * SB, QW = 8 + 4 * NPs;
+  using Rec = BigRecNCF<K>;
+  using Work = BigWork<NPs>;
+  static constexpr int SB = Rec::SB, R = Rec::size, QW = Work::size;
   __host__ __device__ static constexpr bool decayed(int) { return true; }
   // reference theta order [Pm_u, Qm_i, Pg_u, Qg_i]
   __device__ static int ref_index(int side, int a) { return a < K ? side * K + a : 2 * K + side * K + (a - K); }

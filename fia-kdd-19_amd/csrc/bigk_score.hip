@@ -37,6 +37,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     const double* __restrict__ rec, int32_t* __restrict__ rel_idx, double* __restrict__ influence, int K_top,
     int32_t* __restrict__ cand_pos, double* __restrict__ cand_val) {
   constexpr int K = M::K, QB = kBigMfmaQB, XS = QB + 1, NPASS = kScoreRows;
+  using L = typename M::Rec;
   static_assert(NPASS == 4 && QB == 32, "one wave per scoring pass, two 16-query halves");
   __shared__ double Xs[K * XS];        // Xs[k * XS + j]: coordinate seg + k of query j's vector
   __shared__ double Qs[QB][6];         // 1/n, c_q, x.v, r-hat, dup_other, x_bias (MF)
@@ -53,12 +54,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     const int64_t gb = gstart[g] + (int64_t)qblk * QB;
     const int64_t gn = gstart[g + 1] - gb;
     const int nq = gn < QB ? (int)gn : QB;
-    // coordinates [seg, seg + K) of the block's side vectors into Xs (zero past nq)
+    // coordinates [seg, seg + K) of the block's side vectors into Xs (zero past nq): MF x; NCF
+    // x_mlp, then w3g_x_gmf
     auto stage = [&](int seg) {
       for (int t = tid; t < K * QB; t += 256) {
         const int j = t / K, k = t - j * K;
         double v = 0.0;
-        if (j < nq) v = rec[(int64_t)gq[gb + j] * M::R + 8 + sd * M::SB + seg + k];
+        if (j < nq) v = rec[(int64_t)gq[gb + j] * M::R + L::head + sd * L::SB + seg + k];
         Xs[k * XS + j] = v;
       }
     };
@@ -67,13 +69,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void k
     if (tid < QB) {
       const int32_t q = gq[gb + (tid < nq ? tid : nq - 1)];
       const double* __restrict__ R = rec + (int64_t)q * M::R;
-      const double* __restrict__ S = R + 8 + sd * M::SB;
-      Qs[tid][0] = R[0];
-      Qs[tid][1] = R[1];
-      Qs[tid][2] = R[2];
-      Qs[tid][3] = R[3];
-      Qs[tid][4] = M::ncf ? S[2 * K] : S[K + 1];
-      Qs[tid][5] = M::ncf ? 0.0 : S[K];
+      const double* __restrict__ S = L::side(R, sd);
+      Qs[tid][0] = R[L::inv_n];
+      Qs[tid][1] = R[L::c_q];
+      Qs[tid][2] = R[L::x_v];
+      Qs[tid][3] = R[L::rhat];
+      Qs[tid][4] = S[L::dup_other];
+      if constexpr (M::ncf) Qs[tid][5] = 0.0;
+      else Qs[tid][5] = S[L::x_bias];
       const int64_t* qb = qbase + 4 * (int64_t)q;
       Bs[tid][0] = qb[sd] + (int64_t)cidx * kChunk;
       Bs[tid][1] = qb[2 + sd] + cidx;

@@ -17,6 +17,7 @@ template <class M>
 __global__ __launch_bounds__(256) void k_big_prologue(BigArgs A, int64_t Q, double* __restrict__ qwork,
                                                       int32_t* __restrict__ syslist, int32_t* __restrict__ cpllist) {
   constexpr int K = M::K, NPs = M::NPs;
+  using W = typename M::Work;
   __shared__ double red[4];
   __shared__ double z1[M::ncf ? K : 1], d2[M::ncf ? M::H : 1], d1[M::ncf ? K : 1];
   const int tid = threadIdx.x;
@@ -27,13 +28,13 @@ __global__ __launch_bounds__(256) void k_big_prologue(BigArgs A, int64_t Q, doub
     if (ok && A.slot[0]) ok = A.slot[0][u] >= 0 && A.slot[1][i] >= 0;   // not cached: NaN (checked by the ABI)
     const int64_t n = ok ? (A.ptr[0][u + 1] - A.ptr[0][u]) + (A.ptr[1][i + 1] - A.ptr[1][i]) : 0;
     if (n == 0) {
-      if (tid == 0) qw[0] = 0.0;
+      if (tid == 0) qw[W::n] = 0.0;
       continue;
     }
-    double* vu = qw + 8;
-    double* vi = vu + NPs;
-    double* thu = vi + NPs;
-    double* thi = thu + NPs;
+    double* vu = W::v(qw, 0);
+    double* vi = W::v(qw, 1);
+    double* thu = W::theta(qw, 0);
+    double* thi = W::theta(qw, 1);
     double rhat;
     if constexpr (!M::ncf) {
       const float* P = A.t[0] + (int64_t)u * K;
@@ -97,11 +98,11 @@ __global__ __launch_bounds__(256) void k_big_prologue(BigArgs A, int64_t Q, doub
     if (tid == 0) {
       double cdup, rsum;
       A.pairs.lookup((unsigned long long)u * (unsigned long long)A.I + (unsigned long long)i, cdup, rsum);
-      qw[0] = (double)n;
-      qw[1] = cdup;
-      qw[2] = cdup * rhat - rsum;
-      qw[3] = rhat;
-      qw[4] = cdup > 0.0 ? 1.0 : 0.0;
+      qw[W::n] = (double)n;
+      qw[W::cdup] = cdup;
+      qw[W::esum] = cdup * rhat - rsum;
+      qw[W::rhat] = rhat;
+      qw[W::coupled] = cdup > 0.0 ? 1.0 : 0.0;
       if (cdup > 0.0) {
         const int s = atomicAdd(cpllist, 1);
         cpllist[1 + s] = (int32_t)q;
@@ -136,6 +137,8 @@ __global__ __launch_bounds__(solve_threads<NP>()) void k_big_solve(BigArgs A, co
   constexpr int CPT = (NP + kST - 1) / kST;    // backward-solve columns per thread
   constexpr int BW = CPT == 1 && NB == 32 ? 32 : 16;   // backward-solve block (<= NB: staged in W11)
   static_assert(BW <= NB, "backward blocks are staged in W11");
+  using L = typename M::Rec;
+  using W = typename M::Work;
   __shared__ double P[LDR * LDP];
   __shared__ double dd[NP];
   __shared__ double W11[NB * NB];              // W11[j][jj] = L[c0+j][c0+jj] d[c0+jj], jj < j
@@ -149,8 +152,8 @@ __global__ __launch_bounds__(solve_threads<NP>()) void k_big_solve(BigArgs A, co
     const int64_t q = CPL ? code : (code >> 1);
     const int sd = CPL ? 0 : (code & 1);
     const double* __restrict__ qw = qwork + q * M::QW;
-    const double s2n = 2.0 / qw[0], cdup = qw[1], esum = qw[2];
-    const double* __restrict__ vv = qw + 8 + (CPL ? 0 : sd * NPs);   // v of this system
+    const double s2n = 2.0 / qw[W::n], cdup = qw[W::cdup], esum = qw[W::esum];
+    const double* __restrict__ vv = W::v(qw, sd);   // v of this system (coupled: sd = 0, both sides)
     const int32_t u = A.qu[q], i = A.qi[q];
     const double* __restrict__ G0 = A.gram[0] + (int64_t)(A.slot[0] ? A.slot[0][u] : u) * GW;
     const double* __restrict__ G1 = A.gram[1] + (int64_t)(A.slot[1] ? A.slot[1][i] : i) * GW;
@@ -332,8 +335,8 @@ __global__ __launch_bounds__(solve_threads<NP>()) void k_big_solve(BigArgs A, co
     for (int s = 0; s < (CPL ? 2 : 1); ++s) {
       const int side = CPL ? s : sd;
       const double* __restrict__ xsd = xs + (CPL ? s * NPs : 0);
-      const double* __restrict__ vsd = qw + 8 + side * NPs;
-      const double* __restrict__ th = qw + 8 + 2 * NPs + side * NPs;
+      const double* __restrict__ vsd = W::v(qw, side);
+      const double* __restrict__ th = W::theta(qw, side);
       double* __restrict__ xo = xb + q * 2 * NPs + side * NPs;
       double cq = 0.0, xv = 0.0;
       for (int a = tid; a < NPs; a += kST) {
@@ -346,21 +349,20 @@ __global__ __launch_bounds__(solve_threads<NP>()) void k_big_solve(BigArgs A, co
       }
       cq = bsum<kSW>(cq, red);
       xv = bsum<kSW>(xv, red);
-      double* __restrict__ S = R + 8 + side * M::SB;
+      double* __restrict__ S = L::side(R, side);
       if (tid == 0) {
-        R[4 + 2 * side] = A.wd * cq;
-        R[5 + 2 * side] = xv;
+        R[L::cq_of(side)] = A.wd * cq;
+        R[L::xv_of(side)] = xv;
       }
       if constexpr (!M::ncf) {
-        for (int a = tid; a <= K; a += kST) S[a] = xsd[a];
-        if (tid == 0) S[K + 1] = (double)(side ? u : i);
+        for (int a = tid; a <= K; a += kST) S[L::x + a] = xsd[a];
       } else {
         for (int c = tid; c < K; c += kST) {
-          S[c] = xsd[c];
-          S[K + c] = (double)A.t[8][M::H + c] * xsd[K + c];
+          S[L::x_mlp + c] = xsd[c];
+          S[L::w3g_x_gmf + c] = (double)A.t[8][M::H + c] * xsd[K + c];
         }
-        if (tid == 0) S[2 * K] = (double)(side ? u : i);
       }
+      if (tid == 0) S[L::dup_other] = (double)(side ? u : i);
     }
     __syncthreads();   // xs / dd / P are rewritten by the next system
   }
@@ -374,17 +376,19 @@ __global__ __launch_bounds__(64) void k_big_record_x(BigArgs A, int64_t Q, const
                                                      const double* __restrict__ qwork, double* __restrict__ xb,
                                                      double* __restrict__ rec) {
   constexpr int K = M::K, NPs = M::NPs, Ds = M::Ds, D = 2 * Ds;
+  using L = typename M::Rec;
+  using W = typename M::Work;
   const int tid = threadIdx.x;
   for (int64_t w = blockIdx.x; w < 2 * Q; w += gridDim.x) {
     const int64_t q = w >> 1;
     const int sd = (int)(w & 1);
     const double* __restrict__ qw = qwork + q * M::QW;
-    const double* __restrict__ vsd = qw + 8 + sd * NPs;
-    const double* __restrict__ th = qw + 8 + 2 * NPs + sd * NPs;
+    const double* __restrict__ vsd = W::v(qw, sd);
+    const double* __restrict__ th = W::theta(qw, sd);
     const double* __restrict__ xq = x_in + q * D;
     double* __restrict__ xo = xb + q * 2 * NPs + sd * NPs;
     double* __restrict__ R = rec + q * M::R;
-    double* __restrict__ S = R + 8 + sd * M::SB;
+    double* __restrict__ S = L::side(R, sd);
     double cq = 0.0, xv = 0.0;
     for (int a = tid; a < NPs; a += 64) {
       const double xa = a < Ds ? xq[M::ref_index(sd, a)] : 0.0;
@@ -394,19 +398,19 @@ __global__ __launch_bounds__(64) void k_big_record_x(BigArgs A, int64_t Q, const
         xv = fma(xa, vsd[a], xv);
       }
       if constexpr (!M::ncf) {
-        if (a <= K) S[a] = xa;
+        if (a <= K) S[L::x + a] = xa;
       } else {
-        if (a < K) S[a] = xa;
-        else if (a < Ds) S[a] = (double)A.t[8][M::H + (a - K)] * xa;
+        if (a < K) S[L::x_mlp + a] = xa;
+        else if (a < Ds) S[L::w3g_x_gmf + (a - K)] = (double)A.t[8][M::H + (a - K)] * xa;
       }
     }
     cq = wave_sum(cq);
     xv = wave_sum(xv);
     if (tid == 0) {
-      R[4 + 2 * sd] = A.wd * cq;
-      R[5 + 2 * sd] = xv;
+      R[L::cq_of(sd)] = A.wd * cq;
+      R[L::xv_of(sd)] = xv;
       const int32_t u = A.qu[q], i = A.qi[q];
-      S[M::ncf ? 2 * K : K + 1] = (double)(sd ? u : i);
+      S[L::dup_other] = (double)(sd ? u : i);
     }
   }
 }
@@ -417,15 +421,17 @@ __global__ __launch_bounds__(64) void k_big_finish(int64_t Q, const double* __re
                                                    const double* __restrict__ xb, double* __restrict__ rec,
                                                    double* __restrict__ x_out) {
   constexpr int Ds = M::Ds, NPs = M::NPs, D = 2 * Ds;
+  using L = typename M::Rec;
+  using W = typename M::Work;
   for (int64_t q = blockIdx.x; q < Q; q += gridDim.x) {
-    const double n = qwork[q * M::QW];
+    const double n = qwork[q * M::QW + W::n];
     double* R = rec + q * M::R;
     if (threadIdx.x == 0) {
-      R[0] = n > 0.0 ? 1.0 / n : NAN;
+      R[L::inv_n] = n > 0.0 ? 1.0 / n : NAN;
       if (n > 0.0) {
-        R[1] = R[4] + R[6];
-        R[2] = R[5] + R[7];
-        R[3] = qwork[q * M::QW + 3];
+        R[L::c_q] = R[L::cq_u] + R[L::cq_i];
+        R[L::x_v] = R[L::xv_u] + R[L::xv_i];
+        R[L::rhat] = qwork[q * M::QW + W::rhat];
       }
     }
     if (x_out)

@@ -76,8 +76,8 @@ __device__ __forceinline__ SideSys<M, NP> side_sys(const BigArgs& A, int code, c
   const int sd = code & 1;
   const double* __restrict__ qw = qwork + q * M::QW;
   SideSys<M, NP> S;
-  S.s2n = 2.0 / qw[0];
-  S.vv = qw + 8 + sd * M::NPs;
+  S.s2n = 2.0 / qw[M::Work::n];
+  S.vv = M::Work::v(qw, sd);
   if (sd == 0) {
     const int32_t u = A.qu[q];
     S.G = A.gram[0] + (int64_t)(A.slot[0] ? A.slot[0][u] : u) * GW;
@@ -393,8 +393,8 @@ __global__ __launch_bounds__(512) void k_bs_back(BigArgs A, const int32_t* __res
   }
   // padded solution, this side's partial sums and scoring record (as k_big_solve)
   const int32_t u = A.qu[q], i = A.qi[q];
-  const double* __restrict__ vsd = qw + 8 + sd * NPs;
-  const double* __restrict__ th = qw + 8 + 2 * NPs + sd * NPs;
+  const double* __restrict__ vsd = M::Work::v(qw, sd);
+  const double* __restrict__ th = M::Work::theta(qw, sd);
   double* __restrict__ xo = xb + q * 2 * NPs + sd * NPs;
   double cq = 0.0, xv = 0.0;
   for (int a = tid; a < NPs; a += kST) {
@@ -408,21 +408,21 @@ __global__ __launch_bounds__(512) void k_bs_back(BigArgs A, const int32_t* __res
   cq = bsum<kSW>(cq, red);
   xv = bsum<kSW>(xv, red);
   double* __restrict__ R = rec + q * M::R;
-  double* __restrict__ S = R + 8 + sd * M::SB;
+  using L = typename M::Rec;
+  double* __restrict__ S = L::side(R, sd);
   if (tid == 0) {
-    R[4 + 2 * sd] = A.wd * cq;
-    R[5 + 2 * sd] = xv;
+    R[L::cq_of(sd)] = A.wd * cq;
+    R[L::xv_of(sd)] = xv;
   }
   if constexpr (!M::ncf) {
-    for (int a = tid; a <= K; a += kST) S[a] = xs[a];
-    if (tid == 0) S[K + 1] = (double)(sd ? u : i);
+    for (int a = tid; a <= K; a += kST) S[L::x + a] = xs[a];
   } else {
     for (int c = tid; c < K; c += kST) {
-      S[c] = xs[c];
-      S[K + c] = (double)A.t[8][M::H + c] * xs[K + c];
+      S[L::x_mlp + c] = xs[c];
+      S[L::w3g_x_gmf + c] = (double)A.t[8][M::H + c] * xs[K + c];
     }
-    if (tid == 0) S[2 * K] = (double)(sd ? u : i);
   }
+  if (tid == 0) S[L::dup_other] = (double)(sd ? u : i);
 }
 
 // the three launches of the panel at column c0 for systems [w0, w0 + n) of the list

@@ -18,10 +18,24 @@ namespace fia {
 
 constexpr int kCandTile = 256;        // pairs per scoring workgroup, one per thread
 
+// The record query_record writes per query and the pair-scoring kernels of score_cand.hip and
+// total.hip read (in c->rec, but not the scoring record of kern.h).  Offsets in doubles.
+struct CandHead {
+  static constexpr int inv_n = 0;                 // 1 / n_q
+  static constexpr int c_q = 1;                   // wd * x . theta / n_q
+  static constexpr int head = 2;                  // MF: the whole record
+};
+template <int K>
+struct CandRecNCF : CandHead {
+  static constexpr int y_user = head;             // [K] W1[:k]^T x_Pm
+  static constexpr int y_item = head + K;         // [K] W1[k:]^T x_Qm
+  static constexpr int w3g_x_pg = head + 2 * K;   // [K] W3g * x_Pg
+  static constexpr int w3g_x_qg = head + 3 * K;   // [K] W3g * x_Qg
+  static constexpr int size = head + 4 * K;
+};
 template <class M>
 constexpr int cand_rec_size() {
-  // {1 / n_q, c_q}; NCF: + y_user[K], y_item[K], W3g * x_Pg [K], W3g * x_Qg [K]
-  return M::ncf ? 2 + 4 * M::K : 2;
+  return M::ncf ? CandRecNCF<M::K>::size : CandHead::head;
 }
 
 // The record of query (u, i) (ids in range) with inverse HVP xq (reference theta order), by
@@ -49,8 +63,8 @@ __device__ __forceinline__ void query_record(const Args& A, int32_t u, int32_t i
   part = wave_sum(part);
   const double inv_n = 1.0 / (double)n;     // n_q = 0: inf, and x is NaN
   if (lane == 0) {
-    Rq[0] = inv_n;
-    Rq[1] = A.wd * part * inv_n;
+    Rq[CandHead::inv_n] = inv_n;
+    Rq[CandHead::c_q] = A.wd * part * inv_n;
   }
   if constexpr (M::ncf) {
     const float* __restrict__ W1 = A.t[4];
@@ -61,10 +75,11 @@ __device__ __forceinline__ void query_record(const Args& A, int32_t u, int32_t i
         yu = fma((double)W1[(int64_t)j * K + c], xq[j], yu);
         yi = fma((double)W1[(int64_t)(K + j) * K + c], xq[K + j], yi);
       }
-      Rq[2 + c] = yu;
-      Rq[2 + K + c] = yi;
-      Rq[2 + 2 * K + c] = (double)W3g[c] * xq[2 * K + c];
-      Rq[2 + 3 * K + c] = (double)W3g[c] * xq[3 * K + c];
+      using L = CandRecNCF<K>;
+      Rq[L::y_user + c] = yu;
+      Rq[L::y_item + c] = yi;
+      Rq[L::w3g_x_pg + c] = (double)W3g[c] * xq[2 * K + c];
+      Rq[L::w3g_x_qg + c] = (double)W3g[c] * xq[3 * K + c];
     }
   }
 }

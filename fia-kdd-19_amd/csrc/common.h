@@ -233,6 +233,15 @@ struct PhaseEvents {
   std::vector<hipEvent_t> pool;
 };
 
+// First words of a query's scoring record (c->rec), the same at every k; the rest of the record
+// is Rec* of kern.h (small k) and BigRec* of bigk.h (large k).  Offsets in doubles.
+struct RecHead {
+  static constexpr int inv_n = 0;   // 1 / n; NaN: the query has no related rating
+  static constexpr int c_q = 1;     // wd * x . theta over the decayed coordinates
+  static constexpr int x_v = 2;     // x . v
+  static constexpr int rhat = 3;    // r-hat(u, i)
+};
+
 }  // namespace fia
 
 struct fia_ctx {
@@ -247,7 +256,7 @@ struct fia_ctx {
   fia::DevBuf gpart[2];   // partial Grams of long lists (fp64, [n_gslots * GSP])
   bool prepared = false;
   // per-batch scratch
-  fia::DevBuf rec;        // per-query scoring record (fp64)
+  fia::DevBuf rec;        // per-query scoring record (fp64): M::Rec of the model's traits
   fia::DevBuf coff;       // int64 [Q+1] chunk offsets
   fia::DevBuf cdesc;      // ChunkDesc [max chunks]
   fia::DevBuf cand_pos;   // int32 [max chunks * K]
@@ -302,7 +311,7 @@ struct fia_ctx {
   int64_t n_bitems[2] = {0, 0}, n_bcomb[2] = {0, 0}, n_bslots[2] = {0, 0}, n_bcache[2] = {0, 0};
   uint64_t bitems_version = ~0ull;
   int bitems_k = 0;
-  fia::DevBuf qwork;      // double [Q * QW] per-query n, dup terms, r-hat, v, theta
+  fia::DevBuf qwork;      // double [Q * QW] per-query work words (BigWork, bigk.h; NCF k = 16: QPro, kern.h)
   fia::DevBuf xb;         // double [Q * 2 NPs] per-query solution (padded side blocks)
   fia::DevBuf syslist;    // int32 [1 + 2Q] {count, 2q + side ...} uncoupled side systems
   fia::DevBuf cpllist;    // int32 [1 + Q]  {count, q ...} coupled full systems

@@ -88,7 +88,7 @@ __global__ __launch_bounds__(kGdThreads) void k_group_down(BigArgs A, DownArgs D
     const int64_t q = last_at_most(Dn.grp_off, (int64_t)0, Dn.Q - 1, gi);
     double* __restrict__ dw = Dn.dwork + w * down_words<M>();
     double* __restrict__ dA[2] = {Dn.slab + w * 2 * GW, Dn.slab + w * 2 * GW + GW};
-    const double nq = Dn.qwork[q * M::QW];
+    const double nq = Dn.qwork[q * M::QW + M::Work::n];
     if (nq == 0.0) {                                  // (the prologue's verdict: ids out of range, no cache, n = 0)
       if (tid == 0) dw[0] = 2.0;
       continue;
@@ -273,7 +273,7 @@ __global__ __launch_bounds__(solve_threads<2 * M::NPs>()) void k_big_down(BigArg
     const int64_t o = Dn.first + w;            // the output slot: group, or position in rows
     const int64_t q = self ? w : last_at_most(Dn.grp_off, (int64_t)0, Dn.Q - 1, o);
     const double* __restrict__ qw = Dn.qwork + q * M::QW;
-    const double n = qw[0];
+    const double n = qw[M::Work::n];
     const double* __restrict__ dw = Dn.dwork + w * down_words<M>();
     int status;
     double cS = 1.0, eS = 0.0, mS = 2.0;
@@ -306,9 +306,9 @@ __global__ __launch_bounds__(solve_threads<2 * M::NPs>()) void k_big_down(BigArg
       }
       continue;
     }
-    const double s2n = 2.0 / n, cdup = qw[1], esum = qw[2];
-    const double* __restrict__ vv = qw + 8;
-    const double* __restrict__ th = qw + 8 + 2 * NPs;
+    const double s2n = 2.0 / n, cdup = qw[M::Work::cdup], esum = qw[M::Work::esum];
+    const double* __restrict__ vv = M::Work::v(qw, 0);         // both sides, 2 NPs
+    const double* __restrict__ th = M::Work::theta(qw, 0);
     // b_S; a row's own system: sum e_j g_j is e v
     const double wdm = A.wd * (mS / n);
     for (int r = tid; r < NP; r += kST) {

@@ -13,6 +13,42 @@
 namespace fia {
 
 // ------------------------------------------------------------------------------------
+// The per-query scoring record (c->rec) that the solve kernels write and the scoring kernels
+// read: RecHead (common.h), then the block of the user side (sd = 0) and of the item side
+// (sd = 1).  Offsets in doubles; a kernel reads them through its traits, M::Rec.
+// ------------------------------------------------------------------------------------
+template <int K>
+struct RecMF : RecHead {
+  static constexpr int head = 4;
+  // side block, from side(R, sd)
+  static constexpr int theta = 0;               // [K] the side's embedding
+  static constexpr int x = K;                   // [K] x at the embedding coordinates
+  static constexpr int bias = 2 * K;            // b_s + the global bias
+  static constexpr int x_bias = 2 * K + 1;      // x at the bias coordinate
+  static constexpr int dup_other = 2 * K + 2;   // the test pair's other endpoint (an id, as a double)
+  static constexpr int SB = 2 * K + 4;          // (one word of padding)
+  static constexpr int size = head + 2 * SB;
+  template <class T>
+  static constexpr T* side(T* R, int sd) { return R + head + sd * SB; }   // of the record at R
+  // k_score_mf_mfma loads x of either side as double2
+  static_assert((head + x) % 2 == 0 && SB % 2 == 0 && size % 2 == 0, "x of a side starts 16-B aligned");
+};
+template <int K>
+struct RecNCF : RecHead {
+  static constexpr int head = 4;
+  // side block, from side(R, sd)
+  static constexpr int x_mlp = 0;               // [K] x at the MLP embedding (on the k <= 16 mask path
+                                                // k_ncf_rec_y overwrites it with y = W1_side^T x_mlp)
+  static constexpr int w3g_x_gmf = K;           // [K] W3g * x at the GMF embedding
+  static constexpr int dup_other = 2 * K;       // the test pair's other endpoint (an id, as a double)
+  static constexpr int SB = 2 * K + 1;
+  static constexpr int size = head + 2 * SB;
+  static_assert(x_mlp == 0 && w3g_x_gmf == K, "k_solve_col: a side's block coordinate is its offset here");
+  template <class T>
+  static constexpr T* side(T* R, int sd) { return R + head + sd * SB; }   // of the record at R
+};
+
+// ------------------------------------------------------------------------------------
 // model traits
 // ------------------------------------------------------------------------------------
 template <int K_>
@@ -20,9 +56,8 @@ struct MFm {
   static constexpr int K = K_;
   static constexpr int Ds = K + 1;
   static constexpr int D = 2 * Ds;
-  static constexpr int SB = 2 * K + 4;          // per-side record: a, xs, bias, xsb, dup_other, pad
-                                                // (even: x_s starts 16-B aligned for k_score_mf_mfma)
-  static constexpr int R = 4 + 2 * SB;          // header: inv_n, c_q, x.v, r-hat(u,i)
+  using Rec = RecMF<K>;
+  static constexpr int SB = Rec::SB, R = Rec::size;   // doubles per side block, per query
   static constexpr bool ncf = false;
   __device__ static bool decayed(int a) { return a < K; }
   // reference theta order [p_u, q_i, b_u, b_i]
@@ -38,8 +73,8 @@ struct NCFm {
   static constexpr int H2 = K / 2;
   static constexpr int Ds = 2 * K;
   static constexpr int D = 2 * Ds;
-  static constexpr int SB = 2 * K + 1;          // per-side record: x_mlp, W3g * x_gmf, dup_other
-  static constexpr int R = 4 + 2 * SB;          // header: inv_n, c_q, x.v, r-hat(u,i)
+  using Rec = RecNCF<K>;
+  static constexpr int SB = Rec::SB, R = Rec::size;   // doubles per side block, per query
   static constexpr bool ncf = true;
   __device__ static bool decayed(int) { return true; }
   // reference theta order [Pm_u, Qm_i, Pg_u, Qg_i]
@@ -112,9 +147,16 @@ constexpr bool solve_covered() {
   return use_quad_solve<M>() || use_tps<M>() || pair_layout<M>() || use_col_solve<M>() || use_tile_solve<M>();
 }
 
-// doubles per query that k_ncf_query_pro hands to k_solve_rows (NCF k = 16)
+// what k_ncf_query_pro hands to k_solve_rows per query (NCF k = 16; in c->qwork), in doubles
 template <class M>
-constexpr int qpro_stride() { return M::D + 4; }
+struct QPro {
+  static constexpr int v = 0;                   // [D] d r-hat / d theta_t, block order
+  static constexpr int rhat = M::D;             // r-hat(u, i)
+  static constexpr int n = M::D + 1;            // related ratings
+  static constexpr int cdup = M::D + 2;         // > 0: the test pair is a train row
+  static constexpr int pad = M::D + 3;
+  static constexpr int stride = M::D + 4;
+};
 
 // queries per entity-shared work item: 16 for MF k >= 64, where a work item's gathered
 // rows (256 B each) are the dominant traffic and two query blocks would load them twice
@@ -301,7 +343,7 @@ hipError_t launch_gram_combine(fia_ctx* c, int64_t nc0, const int32_t* comb0, in
 // small_solve.hip: the model's side-system solve with its grid rule (MF k = 16: the launch that
 // also runs the scan S and the coupled solves, stamping ps; the others append to `coupled` for
 // launch_coupled_solve, whose dispatch stamps `end`); NCF k = 16's per-query prologue into
-// qpro [Q * qpro_stride]; the records of a given x
+// qpro [Q * QPro::stride]; the records of a given x
 hipError_t launch_side_solve(int model, int k, fia_ctx* c, const ScanArgs& S, const QueryArgs& A, int64_t Q,
                              double* x_out, int32_t* coupled, hipStream_t s, PhaseSpan ps);
 hipError_t launch_coupled_solve(int model, int k, const QueryArgs& A, int64_t Q, double* rec, double* x_out,

@@ -190,7 +190,7 @@ hipError_t query_impl(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
   if constexpr (pair_layout<M>()) {
     if (Q > 0 && !x_in) {
       FIA_HIP_TRY(join_l1(c, s));
-      FIA_HIP_TRY(c->qwork.reserve(sizeof(double) * (size_t)(Q * qpro_stride<M>() + 1), s));
+      FIA_HIP_TRY(c->qwork.reserve(sizeof(double) * (size_t)(Q * QPro<M>::stride + 1), s));
       FIA_HIP_TRY(launch_ncf_query_pro(M::K, A, Q, c->qwork.as<double>(), s));
     }
   }

@@ -52,8 +52,10 @@ namespace {
 // doubles of one (query, side) block and of one query's record
 template <class M>
 constexpr int newton_side() { return M::Ds * M::Ds + 2 * M::Ds; }
+// a query's record (in c->rec, private to this file): these words, then the two side blocks
+constexpr int kNwInvN = 0, kNwCp = 1, kNwCoupled = 2, kNwPad = 3, kNwHead = 4;
 template <class M>
-constexpr int newton_rec() { return 4 + 2 * newton_side<M>(); }
+constexpr int newton_rec() { return kNwHead + 2 * newton_side<M>(); }
 
 struct NewtonArgs {
   int64_t Q;
@@ -161,13 +163,13 @@ __global__ __launch_bounds__(kSolveThreads) void k_newton_query(QueryArgs A, New
     // the record: header, then per side P_ss = (Z^T D^-1 Z)_ss, x'_s, w'_s
     double* __restrict__ Rq = Nw.rec + q * R;
     if (lane == 0) {
-      Rq[0] = inv_n;
-      Rq[1] = cp;
-      Rq[2] = coupled ? 1.0 : 0.0;
-      Rq[3] = 0.0;
+      Rq[kNwInvN] = inv_n;
+      Rq[kNwCp] = cp;
+      Rq[kNwCoupled] = coupled ? 1.0 : 0.0;
+      Rq[kNwPad] = 0.0;
     }
     for (int sd = 0; sd < 2; ++sd) {
-      double* __restrict__ Ps = Rq + 4 + sd * PS;
+      double* __restrict__ Ps = Rq + kNwHead + sd * PS;
       const int o = sd * Ds;
       for (int t = lane; t < Ds * (Ds + 1) / 2; t += kSolveThreads) {
         int a = (int)((sqrt(8.0 * t + 1.0) - 1.0) * 0.5);
@@ -195,7 +197,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_newton_query(QueryArgs A, New
       double* __restrict__ Pl = H;                    // [Ds][Ds]
       double* __restrict__ Yl = H + Ds * Ds;          // [Ds][K]
       for (int sd = 0; sd < 2; ++sd) {
-        double* __restrict__ Ps = Rq + 4 + sd * PS;
+        double* __restrict__ Ps = Rq + kNwHead + sd * PS;
         const double* __restrict__ W = sW1 + sd * K * K;        // W[a][c] = T[a][c], a, c < K
         const int o = sd * Ds;
         __threadfence_block();                        // P_ss as the lanes above stored it
@@ -296,9 +298,9 @@ __global__ __launch_bounds__(64) void k_newton_score(QueryArgs A, NewtonArgs Nw)
     const int64_t q = d.q;
     const int32_t u = A.qu[q], i = A.qi[q];
     const double* __restrict__ Rq = Nw.rec + q * R;
-    const double* __restrict__ Ps = Rq + 4 + sd * PS;
-    const double inv_n = Rq[0], cp = Rq[1], c2 = 2.0 * inv_n;
-    const int32_t dup = Rq[2] > 0.0 ? (sd == 0 ? i : u) : -1;
+    const double* __restrict__ Ps = Rq + kNwHead + sd * PS;
+    const double inv_n = Rq[kNwInvN], cp = Rq[kNwCp], c2 = 2.0 * inv_n;
+    const int32_t dup = Rq[kNwCoupled] > 0.0 ? (sd == 0 ? i : u) : -1;
     // A operand: lane (row cn of block rb, k-group kk) holds P[16 rb + cn][kk + 4 s]; and the
     // lane's coordinates kk + 4 s of x'_s and w'_s
     double pa[RB][KS], xs[KS], ws[KS];

@@ -82,7 +82,8 @@ __device__ __forceinline__ double cand_value_mf(const CandArgs& A, const double*
   double r, su, si;
   coop_dots<K, false, D, 0, K>(valid, a, b, (int)q, on_u, on_i, A.t[0], A.t[1], A.x, nullptr, r, su, si);
   if (!valid) return NAN;
-  const double inv_n = rec[q * 2], cq = rec[q * 2 + 1];
+  constexpr int R = CandHead::head;   // MF: the header is the record
+  const double inv_n = rec[q * R + CandHead::inv_n], cq = rec[q * R + CandHead::c_q];
   const double* __restrict__ xq = A.x + q * D;
   r += (double)A.t[2][a] + (double)A.t[3][b] + (double)A.t[4][0];
   if (on_u) su += xq[2 * K];
@@ -99,11 +100,11 @@ __device__ __forceinline__ double cand_value_ncf(const CandArgs& A, const double
                                                  const NCFWeights<(K <= 64 ? K : 2)>& w, int64_t q, int32_t a,
                                                  int32_t b, float y, bool on_u, bool on_i, double rg, double sg,
                                                  const double* __restrict__ z1col) {
-  constexpr int R = 2 + 4 * K;
-  const double* __restrict__ Rq = rec + q * R;
-  const double inv_n = Rq[0], cq = Rq[1];
+  using L = CandRecNCF<K>;
+  const double* __restrict__ Rq = rec + q * L::size;
+  const double inv_n = Rq[L::inv_n], cq = Rq[L::c_q];
   double r, s;
-  cand_core_ncf<K>(A, w, a, b, on_u, on_i, Rq + 2, Rq + 2 + K, z1col, r, s);
+  cand_core_ncf<K>(A, w, a, b, on_u, on_i, Rq + L::y_user, Rq + L::y_item, z1col, r, s);
   s += sg;
   r += rg + (double)A.t[9][0];
   const double e = r - (double)y;
@@ -152,7 +153,10 @@ __global__ __launch_bounds__(kCandTile) void k_cand_score(CandArgs A, const doub
   }
   // (whole waves from here: the row gathers are cooperative)
   if constexpr (M::ncf) {
+    // (written out: the layout's names as template arguments reorder this kernel's instructions)
     constexpr int R = 2 + 4 * KK;
+    static_assert(R == CandRecNCF<KK>::size && 2 + 2 * KK == CandRecNCF<KK>::w3g_x_pg &&
+                      2 + 3 * KK == CandRecNCF<KK>::w3g_x_qg, "the record of cand.h");
     bool on_u = false, on_i = false;
     if (valid) {
       on_u = a == A.qu[q];

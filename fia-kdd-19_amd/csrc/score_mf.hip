@@ -86,6 +86,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRunsWaves))
     double* __restrict__ influence, int K_top, int32_t* __restrict__ cand_pos, double* __restrict__ cand_val) {
   static_assert(!M::ncf && M::K <= 16 && M::K % 4 == 0, "MF k in {8, 16}");
   constexpr int K = M::K, RT = kRunChunk / 64, NA = K / 4;
+  using L = typename M::Rec;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // bytes per rating of the two outputs (0: the caller passed NULL, include/fia.h)
@@ -150,11 +151,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRunsWaves))
     // own embedding a and b_e + g (scalar loads)
     double g[RT][K], e2[RT];
     {
-      const double* __restrict__ Sh = rec + (int64_t)q0 * M::R + 4 + sd * M::SB;
+      const double* __restrict__ Sh = L::side(rec + (int64_t)q0 * M::R, sd);
       double av[K];
 #pragma unroll
-      for (int c = 0; c < K; ++c) av[c] = Sh[c];
-      const double bias_s = Sh[2 * K];
+      for (int c = 0; c < K; ++c) av[c] = Sh[L::theta + c];
+      const double bias_s = Sh[L::bias];
 #pragma unroll
       for (int r = 0; r < RT; ++r) {
         double dot = 0.0;
@@ -183,14 +184,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRunsWaves))
     auto words = [&](int32_t qj) {
       Words w;
       const double* __restrict__ Rj = rec + (int64_t)qj * M::R;
-      const double* __restrict__ Sj = Rj + 4 + sd * M::SB;
+      const double* __restrict__ Sj = L::side(Rj, sd);
       const int64_t* __restrict__ qb = qbase + 4 * (int64_t)qj;
 #pragma unroll
-      for (int c = 0; c < K; ++c) w.x[c] = Sj[K + c];
-      w.inv_n = Rj[0];
-      w.cq = Rj[1];
-      w.xsb = Sj[2 * K + 1];
-      w.dup = Sj[2 * K + 2];
+      for (int c = 0; c < K; ++c) w.x[c] = Sj[L::x + c];
+      w.inv_n = Rj[L::inv_n];
+      w.cq = Rj[L::c_q];
+      w.xsb = Sj[L::x_bias];
+      w.dup = Sj[L::dup_other];
       w.ou = qb[0];
       w.oi = qb[1];
       w.slot = qb[2 + sd];
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRunsWaves))
       if (__builtin_expect(__ballot(anyd) != 0, 0)) {
         // the test pair's own train row: e = r-hat(u,i) - y, s = x . v (as in the solve's
         // record), both of its copies in rel bit-identical
-        const double xv = Rj[2], rhat_ui = Rj[3];
+        const double xv = Rj[L::x_v], rhat_ui = Rj[L::rhat];
         const float* __restrict__ rat = A.rating[sd] + d.list_base;
 #pragma unroll
         for (int r = 0; r < RT; ++r)
@@ -354,6 +355,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRunsWaves))
     double* __restrict__ influence, int K_top, int32_t* __restrict__ cand_pos, double* __restrict__ cand_val) {
   static_assert(mask_path<M>() && M::K % 4 == 0, "NCF k in {8, 16}");
   constexpr int K = M::K, NA = K / 4, CH = kNcfRunChunk;
+  using L = typename M::Rec;
   static_assert(CH == 64, "one rating per lane");
   const int lane = threadIdx.x & 63;
   const int n_inf = influence ? 8 : 0, n_rel = rel_idx ? 4 : 0;
@@ -418,22 +420,22 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRunsWaves))
     do {
       const int32_t qj = q0 + j;
       const double* __restrict__ Rj = rec + (int64_t)qj * M::R;
-      const double* __restrict__ Sj = Rj + 4 + sd * M::SB;
+      const double* __restrict__ Sj = L::side(Rj, sd);
       double s1 = 0.0, s2 = 0.0;
 #pragma unroll
       for (int c = 0; c < K; ++c) {
-        s1 = fma(Sj[c], d1[c], s1);
-        s2 = fma(Sj[K + c], g[c], s2);
+        s1 = fma(Sj[L::x_mlp + c], d1[c], s1);          // y (k_ncf_rec_y)
+        s2 = fma(Sj[L::w3g_x_gmf + c], g[c], s2);
       }
-      const double inv_nj = Rj[0], cqj = Rj[1];
-      const int32_t dupj = (int32_t)Sj[2 * K];
+      const double inv_nj = Rj[L::inv_n], cqj = Rj[L::c_q];
+      const int32_t dupj = (int32_t)Sj[L::dup_other];
       const int64_t* __restrict__ qb = qbase + 4 * (int64_t)qj;
       const int64_t ou = qb[0], oi = qb[1], slot0 = qb[2 + sd];
       const int64_t obj = sd ? oi : ou;
       double infl = (2.0 * e * (s1 + s2) + cqj) * inv_nj;
       if (__builtin_expect(__ballot(o == dupj && lane < len) != 0, 0)) {
         // the test pair's own train row: e = r-hat(u,i) - y, s = x . v (the solve's record)
-        if (o == dupj && lane < len) infl = (2.0 * (Rj[3] - (double)y) * Rj[2] + cqj) * inv_nj;
+        if (o == dupj && lane < len) infl = (2.0 * (Rj[L::rhat] - (double)y) * Rj[L::x_v] + cqj) * inv_nj;
       }
       const int32_t co = (int32_t)(d.out_base - (sd ? qbase[4 * (int64_t)q0 + 1] : qbase[4 * (int64_t)q0]));
       {

@@ -100,6 +100,7 @@ __global__ __launch_bounds__(kScoreThreads) __attribute__((amdgpu_waves_per_eu(3
   static_assert(kScoreThreads == 64 * kWgBlocks, "one wave per query block");
   static_assert(kUnroll % kRing == 0 && kUnroll % 4 == 0 && kUnroll == kBlkRing * kBlkTiles, "ring periods");
   constexpr int K = M::K, KS = K / 4, NF4 = KS / 4, TPC = kChunk / 16;
+  using L = typename M::Rec;
   constexpr int SG = K / 4;                // 16-B pieces per row
   constexpr int RPW = 64 / SG;             // rows one fetch instruction covers
   constexpr int FW = 16 / RPW;             // waves whose pieces are the tile (k = 64: four; k = 32: two)
@@ -166,8 +167,10 @@ __global__ __launch_bounds__(kScoreThreads) __attribute__((amdgpu_waves_per_eu(3
     if (nq > 0) {
       {
         const int32_t q = gq[gb + (cn < nq ? cn : nq - 1)];
+        // (the side base written out, here and below: L::side() reorders this kernel's loads)
+        static_assert((L::head + L::x) % 2 == 0 && L::SB % 2 == 0 && M::R % 2 == 0 && KS % 2 == 0, "16-B loads");
         const double2* src =
-            reinterpret_cast<const double2*>(rec + (int64_t)q * M::R + 4 + sd * M::SB + K + KS * kk);
+            reinterpret_cast<const double2*>(rec + (int64_t)q * M::R + L::head + sd * L::SB + L::x + KS * kk);
 #pragma unroll
         for (int f = 0; f < KS / 2; ++f) {
           const double2 t = src[f];
@@ -188,8 +191,8 @@ __global__ __launch_bounds__(kScoreThreads) __attribute__((amdgpu_waves_per_eu(3
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const double* __restrict__ R = rec + (int64_t)qr[r] * M::R;
-        const double inv_n = R[0];
-        const int32_t dup_other = (int32_t)R[4 + sd * M::SB + 2 * K + 2];
+        const double inv_n = R[L::inv_n];
+        const int32_t dup_other = (int32_t)R[L::head + sd * L::SB + L::dup_other];
         const longlong2* __restrict__ qb = reinterpret_cast<const longlong2*>(qbase + 4 * (int64_t)qr[r]);
         const longlong2 q01 = qb[0], q23 = qb[1];          // {out base user, item}, {slot base user, item}
         // the row's output run starts at element ob0 (< 2^32: fia_query_batch's batch bound)
@@ -197,8 +200,8 @@ __global__ __launch_bounds__(kScoreThreads) __attribute__((amdgpu_waves_per_eu(3
         if (cn == 0) {
           double* __restrict__ w4 = sQ[wave][kk + 4 * r];
           w4[0] = 2.0 * inv_n;
-          w4[1] = R[1] * inv_n;
-          w4[2] = R[4 + sd * M::SB + 2 * K + 1];
+          w4[1] = R[L::c_q] * inv_n;
+          w4[2] = R[L::head + sd * L::SB + L::x_bias];
           w4[3] = __longlong_as_double((long long)(((unsigned long long)ob0 << 32) |
                                                     (uint32_t)(qv[r] ? dup_other : -1)));
         }
@@ -321,7 +324,7 @@ __global__ __launch_bounds__(kScoreThreads) __attribute__((amdgpu_waves_per_eu(3
           const int32_t q = gq[gb + kk + 4 * r];
           const double* __restrict__ R = rec + (int64_t)q * M::R;
           const double y = (double)rat[p];
-          val[r] = fma((R[3] - y) * al[r], R[2], be[r]);
+          val[r] = fma((R[L::rhat] - y) * al[r], R[L::x_v], be[r]);
         }
       }
       // rotate each row by its misalignment dl: lane cn takes element (cn - dl) & 15 -- of

@@ -46,6 +46,7 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_grouped_mf(
     int32_t* __restrict__ cand_pos, double* __restrict__ cand_val) {
   static_assert(!M::ncf && M::K % 4 == 0, "MF, k a multiple of 4");
   constexpr int K = M::K, RT = kScoreRows, QB = query_block<M>(), CK = 4;
+  using L = typename M::Rec;
   constexpr int NSV = (K + 1 + 63) / 64;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_grouped_mf(
 #pragma unroll
       for (int j = 0; j < NQ; ++j) {
         const int32_t q = gq[gb + (j < nq ? j : nq - 1)];
-        xq[j] = rec + (int64_t)q * M::R + 4 + sd * M::SB;
+        xq[j] = L::side(rec + (int64_t)q * M::R, sd);
       }
       double ea[RT], acc[NQ][RT];
 #pragma unroll
@@ -130,7 +131,7 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_grouped_mf(
         for (int j = 0; j < NQ; ++j) {
 #pragma unroll
           for (int cc = 0; cc < CK; ++cc) {
-            const double xc = xq[j][K + c0 + cc];  // scalar load, SGPR operand
+            const double xc = xq[j][L::x + c0 + cc];  // scalar load, SGPR operand
 #pragma unroll
             for (int r = 0; r < RT; ++r) acc[j][r] = fma(xc, gd[r][cc], acc[j][r]);
           }
@@ -149,8 +150,8 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_grouped_mf(
         if (j >= nq) continue;
         const int32_t q = gq[gb + j];
         const double* __restrict__ R = rec + (int64_t)q * M::R;
-        const double inv_n = R[0], cq = R[1], xv = R[2], rhat_ui = R[3];
-        const double xsb = xq[j][2 * K + 1], dup_o = xq[j][2 * K + 2];
+        const double inv_n = R[L::inv_n], cq = R[L::c_q], xv = R[L::x_v], rhat_ui = R[L::rhat];
+        const double xsb = xq[j][L::x_bias], dup_o = xq[j][L::dup_other];
         const int64_t* __restrict__ qb = qbase + 4 * (int64_t)q;
         const int64_t obj = qb[sd] + (int64_t)cidx * kChunk, cbj = qb[2 + sd] + cidx;
         const int64_t poj = sd ? qb[1] - qb[0] : 0;   // |R_u| precedes item-side positions
@@ -226,6 +227,7 @@ __global__ __launch_bounds__(256) void k_ncf_d1_table(const float* __restrict__ 
 template <class M>
 __global__ __launch_bounds__(256) void k_ncf_rec_y(int64_t Q, const float* __restrict__ W1, double* __restrict__ rec) {
   constexpr int K = M::K;
+  using L = typename M::Rec;
   // W1 as fp64 in LDS: read per use as a broadcast (the per-use scalar loads of the fp32
   // table exposed one memory latency per weight: 20 us at yelp-ex)
   __shared__ double w1[2 * K * K];
@@ -235,7 +237,7 @@ __global__ __launch_bounds__(256) void k_ncf_rec_y(int64_t Q, const float* __res
   if (t >= 2 * Q) return;
   const int64_t q = t >> 1;
   const int sd = (int)(t & 1);
-  double* __restrict__ S = rec + q * M::R + 4 + sd * M::SB;
+  double* __restrict__ S = L::side(rec + q * M::R, sd) + L::x_mlp;   // x_mlp in, y out
   double x[K];
 #pragma unroll
   for (int a = 0; a < K; ++a) x[a] = S[a];
@@ -267,6 +269,7 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_ncf(
     int32_t* __restrict__ cand_pos, double* __restrict__ cand_val) {
   static_assert(M::ncf && M::K == 32, "the NCF k = 32 kernel: g_mlp stored per list position (no mask path)");
   constexpr int K = M::K, RT = kScoreRows, QB = kQueryBlock, CK = 4;
+  using L = typename M::Rec;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t n_items = wstart[nE];
@@ -338,7 +341,7 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_ncf(
 #pragma unroll
       for (int j = 0; j < NQ; ++j) {
         const int32_t q = gq[gb + (j < nq ? j : nq - 1)];
-        xq[j] = rec + (int64_t)q * M::R + 4 + sd * M::SB;
+        xq[j] = L::side(rec + (int64_t)q * M::R, sd);
       }
       double acc[NQ][RTE];
 #pragma unroll
@@ -365,8 +368,8 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_ncf(
 #pragma unroll
           for (int c2 = 0; c2 < CK / 2; ++c2) {
             // scalar loads: x_mlp and W3g * x_gmf as SGPR operands (no LDS)
-            const double ax = xq[j][c0 + 2 * c2], ay = xq[j][c0 + 2 * c2 + 1];
-            const double bx = xq[j][K + c0 + 2 * c2], by = xq[j][K + c0 + 2 * c2 + 1];
+            const double ax = xq[j][L::x_mlp + c0 + 2 * c2], ay = xq[j][L::x_mlp + c0 + 2 * c2 + 1];
+            const double bx = xq[j][L::w3g_x_gmf + c0 + 2 * c2], by = xq[j][L::w3g_x_gmf + c0 + 2 * c2 + 1];
 #pragma unroll
             for (int r = 0; r < RTE; ++r) {
               acc[j][r] = fma(ax, gm_[r][2 * c2], acc[j][r]);
@@ -382,8 +385,8 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_ncf(
         if (j >= nq) continue;   // padding columns (copies of the last query)
         const int32_t q = gq[gb + j];
         const double* __restrict__ Rj = rec + (int64_t)q * M::R;
-        const double inv_n = Rj[0], cq = Rj[1], xv = Rj[2], rhat_ui = Rj[3];
-        const double dup_o = xq[j][2 * K];
+        const double inv_n = Rj[L::inv_n], cq = Rj[L::c_q], xv = Rj[L::x_v], rhat_ui = Rj[L::rhat];
+        const double dup_o = xq[j][L::dup_other];
         const int64_t* __restrict__ qb = qbase + 4 * (int64_t)q;
         const int64_t obj = qb[sd] + (int64_t)cidx * kChunk, cbj = qb[2 + sd] + cidx;
         const int64_t poj = sd ? qb[1] - qb[0] : 0;   // |R_u| precedes item-side positions

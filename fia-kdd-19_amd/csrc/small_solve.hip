@@ -14,6 +14,22 @@
 namespace fia {
 namespace {
 
+// 1 / d: v_rcp_f64 and two Newton steps, instead of an IEEE division sequence on a solve's
+// critical path
+__device__ __forceinline__ double rcp_nr2(double d) {
+  double r = __builtin_amdgcn_rcp(d);
+  r = fma(r, fma(-d, r, 1.0), r);
+  r = fma(r, fma(-d, r, 1.0), r);
+  return r;
+}
+
+// query q joins the coupled list {count, q_0, q_1, ...}: its test pair is a train row, the
+// full-D k_solve finishes it
+__device__ __forceinline__ void coupled_append(int32_t* __restrict__ list, int64_t q) {
+  const int slot = atomicAdd(list, 1);
+  list[1 + slot] = (int32_t)q;
+}
+
 // Record + x_out of one solved query (first wave only, 64 lanes): v = the solution in
 // block order [user block (Ds) | item block (Ds)]
 template <class M>
@@ -22,6 +38,7 @@ __device__ void solve_epilogue(const QueryArgs& A, int64_t q, int32_t u, int32_t
                                const double* __restrict__ v, const NCFWeights<M::ncf ? M::K : 2>& w,
                                double* __restrict__ R, double* __restrict__ x_out) {
   constexpr int K = M::K, Ds = M::Ds, D = M::D;
+  using L = typename M::Rec;
   const int lane = threadIdx.x & 63;
   if (x_out)
     for (int a = lane; a < D; a += kSolveThreads) x_out[q * D + M::ref_index(a)] = v[a];
@@ -38,38 +55,38 @@ __device__ void solve_epilogue(const QueryArgs& A, int64_t q, int32_t u, int32_t
   // its copies in rel (user side and item side) get bit-identical influence, as the
   // reference's per-row sess.run gives them (mf:240-246).
   if (lane == 0) {
-    R[0] = 1.0 / (double)n;
-    R[1] = cq;
-    R[2] = xg_user + xg_item;
-    R[3] = rhat_ui;
+    R[L::inv_n] = 1.0 / (double)n;
+    R[L::c_q] = cq;
+    R[L::x_v] = xg_user + xg_item;
+    R[L::rhat] = rhat_ui;
   }
-  double* S0 = R + 4;
-  double* S1 = R + 4 + M::SB;
+  double* S0 = L::side(R, 0);
+  double* S1 = L::side(R, 1);
   if constexpr (!M::ncf) {
     const double gb = (double)A.t[4][0];
     for (int a = lane; a < K; a += kSolveThreads) {
-      S0[a] = th[a];              // p_u
-      S0[K + a] = v[a];           // x_pu
-      S1[a] = th[Ds + a];         // q_i
-      S1[K + a] = v[Ds + a];      // x_qi
+      S0[L::theta + a] = th[a];         // p_u
+      S0[L::x + a] = v[a];              // x_pu
+      S1[L::theta + a] = th[Ds + a];    // q_i
+      S1[L::x + a] = v[Ds + a];         // x_qi
     }
     if (lane == 0) {
-      S0[2 * K] = th[K] + gb;     S1[2 * K] = th[Ds + K] + gb;
-      S0[2 * K + 1] = v[K];       S1[2 * K + 1] = v[Ds + K];
-      S0[2 * K + 2] = (double)i;  S1[2 * K + 2] = (double)u;
+      S0[L::bias] = th[K] + gb;         S1[L::bias] = th[Ds + K] + gb;
+      S0[L::x_bias] = v[K];             S1[L::x_bias] = v[Ds + K];
+      S0[L::dup_other] = (double)i;     S1[L::dup_other] = (double)u;
     }
   } else {
     // x . g_j = x_mlp . g_mlp,j + (W3g * x_gmf) . gmf_other(j)  (k_score_ncf)
     constexpr int H2 = K / 2;
     for (int c = lane; c < K; c += kSolveThreads) {
-      S0[c] = v[c];
-      S1[c] = v[Ds + c];
+      S0[L::x_mlp + c] = v[c];
+      S1[L::x_mlp + c] = v[Ds + c];
       const double w3g = w.W3[H2 + c];
-      S0[K + c] = w3g * v[K + c];
-      S1[K + c] = w3g * v[Ds + K + c];
+      S0[L::w3g_x_gmf + c] = w3g * v[K + c];
+      S1[L::w3g_x_gmf + c] = w3g * v[Ds + K + c];
     }
     if (lane == 0) {
-      S0[2 * K] = (double)i;  S1[2 * K] = (double)u;
+      S0[L::dup_other] = (double)i;  S1[L::dup_other] = (double)u;
     }
   }
 }
@@ -105,7 +122,7 @@ __device__ __forceinline__ void solve_full_wave(const QueryArgs& A, int64_t q, d
   if (n == 0) {
     if (x_out)
       for (int a = lane; a < D; a += kSolveThreads) x_out[q * D + a] = NAN;
-    if (lane == 0) R[0] = NAN;
+    if (lane == 0) R[M::Rec::inv_n] = NAN;
     return;
   }
 
@@ -194,7 +211,7 @@ __global__ __launch_bounds__(kSolveThreads) void k_record_x(QueryArgs A, int64_t
     if (n == 0) {
       if (x_out)
         for (int a = lane; a < D; a += kSolveThreads) x_out[q * D + a] = NAN;
-      if (lane == 0) R[0] = NAN;
+      if (lane == 0) R[M::Rec::inv_n] = NAN;
       continue;
     }
     const double rhat_ui = solve_prologue<M, kSolveThreads>(A, u, i, th, g, sh, w, sW1, sb1);
@@ -331,9 +348,7 @@ __device__ void tile_factor(int g, int c, d4_t (&U)[NT * (NT + 1) / 2], d4_t (&R
       }
       wave_lds_sync();
       const double dk = Pb[k * PS];
-      double ij = __builtin_amdgcn_rcp(dk);
-      ij = fma(ij, fma(-dk, ij, 1.0), ij);
-      ij = fma(ij, fma(-dk, ij, 1.0), ij);
+      const double ij = rcp_nr2(dk);
       double f[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -482,7 +497,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(tile_waves<
       if (wv == 0) {
         if (x_out)
           for (int a = lane; a < D; a += 64) x_out[q * D + a] = NAN;
-        if (lane == 0) rec[q * M::R] = NAN;
+        if (lane == 0) rec[q * M::R + M::Rec::inv_n] = NAN;
       }
       continue;
     }
@@ -497,10 +512,7 @@ __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(tile_waves<
     double cdup, rsum;
     A.pairs.probe_finish(pkey, ph, pk, cdup, rsum);
     if (cdup > 0.0) {
-      if (threadIdx.x == 0) {
-        const int slot = atomicAdd(coupled_out, 1);
-        coupled_out[1 + slot] = (int32_t)q;
-      }
+      if (threadIdx.x == 0) coupled_append(coupled_out, q);
       continue;
     }
     if constexpr (!EARLY) tile_load<NT, EXTRA, pair_layout<M>()>(A.gram[wv] + (int64_t)ent * GSP, lg, lc, U, hr, hc, hb);
@@ -619,9 +631,7 @@ __device__ __forceinline__ void ncf2_publish(const double (&c0)[N], const double
   Pb[cb] = c1[J];
   if (ca == J || cb == J) {                        // the diagonal's owner: y_J and 1/d_J
     const double dj = ca == J ? c0[J] : c1[J];
-    double ij = __builtin_amdgcn_rcp(dj);
-    ij = fma(ij, fma(-dj, ij, 1.0), ij);
-    ij = fma(ij, fma(-dj, ij, 1.0), ij);
+    const double ij = rcp_nr2(dj);
     Pb[N] = ca == J ? y0 : y1;
     Pb[N + 1] = ij;
   }
@@ -773,12 +783,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(col_waves<M>
     }
     wave_lds_sync();
     // ---- record + x_out, lane-parallel: this lane holds x at coordinates ca, cb of side sd
-    // of query qs (record layout: solve_epilogue) ----
+    // of query qs ----
     {
       const int64_t q = q0 + qs;
       const int64_t nn = s_n[qs];
       const bool live_q = q < Q && nn > 0 && !(s_cd[qs] > 0.0);
       constexpr int H2 = K / 2;
+      using L = typename M::Rec;
       // x . theta over the decayed coordinates (all of NCF's) and x . v, summed over the query's
       // two systems (2 LS lanes)
       double cq = fma(y0, th[qs][sd * N + ca], y1 * th[qs][sd * N + cb]);
@@ -787,17 +798,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(col_waves<M>
       xv = sys_sum<LS>(xv);
       if (live_q) {
         double* __restrict__ R = rec + q * M::R;
-        double* __restrict__ S = R + 4 + sd * M::SB;
+        double* __restrict__ S = L::side(R, sd);
         if (sd == 0 && t == 0) {
-          R[0] = 1.0 / (double)nn;
-          R[1] = cq * A.wd;
-          R[2] = xv;
-          R[3] = rh[qs];
+          R[L::inv_n] = 1.0 / (double)nn;
+          R[L::c_q] = cq * A.wd;
+          R[L::x_v] = xv;
+          R[L::rhat] = rh[qs];
         }
-        // block coordinates: [0, K) mlp, [K, 2K) gmf; the record holds x_mlp and W3g * x_gmf
+        // block coordinates: [0, K) mlp, [K, 2K) gmf = x_mlp and w3g_x_gmf, which lie back to back
         S[ca] = ca < K ? y0 : w.W3[H2 + ca - K] * y0;
         S[cb] = cb < K ? y1 : w.W3[H2 + cb - K] * y1;
-        if (t == 0) S[2 * K] = (double)(sd ? s_u[qs] : s_i[qs]);
+        if (t == 0) S[L::dup_other] = (double)(sd ? s_u[qs] : s_i[qs]);
         if (x_out) {
           x_out[q * D + M::ref_index(sd * Ds + ca)] = y0;
           x_out[q * D + M::ref_index(sd * Ds + cb)] = y1;
@@ -807,10 +818,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(col_waves<M>
           x_out[q * D + sd * Ds + ca] = NAN;
           x_out[q * D + sd * Ds + cb] = NAN;
         }
-        if (sd == 0 && t == 0) rec[q * M::R] = NAN;
-      } else if (q < Q && sd == 0 && t == 0) {      // coupled: the full-D solve finishes it
-        const int slot = atomicAdd(coupled_out, 1);
-        coupled_out[1 + slot] = (int32_t)q;
+        if (sd == 0 && t == 0) rec[q * M::R + M::Rec::inv_n] = NAN;
+      } else if (q < Q && sd == 0 && t == 0) {
+        coupled_append(coupled_out, q);
       }
     }
   }
@@ -820,7 +830,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(col_waves<M>
 // NCF k = 16 side-system solve by rows (the default for NCF k = 16), two launches:
 //  k_ncf_query_pro: one THREAD per query -- n, the pair-set lookup, r-hat(u,i) and
 //    v = d r-hat / d theta_t in block order (ncf:102-145, 181-191; gnn:155) into
-//    qpro[q] = {v[D] | r-hat, n, c_dup, 0}.  The MLP is ~0.8 k FMAs per query; computed
+//    qpro[q] (QPro, kern.h).  The MLP is ~0.8 k FMAs per query; computed
 //    wave-cooperatively inside the solve (k_solve_col) it took a fifth of that kernel
 //    (LDS round trips between tiny loops, by s_memtime stamps of a diagnostic build).
 //  k_solve_rows: 16 lanes per side system (4 systems = 2 queries per wave); lane t owns rows
@@ -838,7 +848,8 @@ constexpr int kRowsWaves = 2;      // 198 VGPRs, no spills; at 3 waves (168 VGPR
 
 template <class M>
 __global__ __launch_bounds__(256) void k_ncf_query_pro(QueryArgs A, int64_t Q, double* __restrict__ qpro) {
-  constexpr int K = M::K, H2 = K / 2, Ds = M::Ds, D = M::D, PS = qpro_stride<M>();
+  constexpr int K = M::K, H2 = K / 2, Ds = M::Ds;
+  using PL = QPro<M>;
   constexpr int EPL = H2 / 4, GPL = 2 * K / 4, FPL = K / 4;   // per-lane shares of a query's outputs
   static_assert(H2 % 4 == 0, "k a multiple of 8");
   // the MLP weights as fp64 in LDS, read per use as broadcasts (per-use scalar loads of the
@@ -878,7 +889,7 @@ __global__ __launch_bounds__(256) void k_ncf_query_pro(QueryArgs A, int64_t Q, d
   double d2[H2];
 #pragma unroll
   for (int e = 0; e < H2; ++e) d2[e] = __shfl(d2o[e / 4], base + (e & 3));
-  double* __restrict__ P = qpro + q * PS;
+  double* __restrict__ P = qpro + q * PL::stride;
   const float* __restrict__ pg = A.t[2] + (int64_t)uu * K;
   const float* __restrict__ qg = A.t[3] + (int64_t)ii * K;
 #pragma unroll
@@ -887,8 +898,8 @@ __global__ __launch_bounds__(256) void k_ncf_query_pro(QueryArgs A, int64_t Q, d
     const double w3g = sW3[H2 + a], pga = (double)pg[a], qga = (double)qg[a];
     part += w3g * pga * qga;
     if (qok) {
-      P[K + a] = w3g * qga;            // d r / d Pg_u = W3g * Qg_i
-      P[Ds + K + a] = w3g * pga;       // d r / d Qg_i = W3g * Pg_u
+      P[PL::v + K + a] = w3g * qga;            // d r / d Pg_u = W3g * Qg_i
+      P[PL::v + Ds + K + a] = w3g * pga;       // d r / d Qg_i = W3g * Pg_u
     }
   }
   double d1[K];
@@ -905,7 +916,7 @@ __global__ __launch_bounds__(256) void k_ncf_query_pro(QueryArgs A, int64_t Q, d
     double s = 0.0;
 #pragma unroll
     for (int c = 0; c < K; ++c) s = fma(sW1[a * K + c], d1[c], s);
-    if (qok) P[a < K ? a : Ds + (a - K)] = s;
+    if (qok) P[PL::v + (a < K ? a : Ds + (a - K))] = s;
   }
   part += __shfl_xor(part, 1);
   part += __shfl_xor(part, 2);
@@ -913,10 +924,10 @@ __global__ __launch_bounds__(256) void k_ncf_query_pro(QueryArgs A, int64_t Q, d
     const int64_t n = ok ? (A.ptr[0][uu + 1] - A.ptr[0][uu]) + (A.ptr[1][ii + 1] - A.ptr[1][ii]) : 0;
     double cdup, rsum;
     A.pairs.lookup((unsigned long long)uu * (unsigned long long)A.I + (unsigned long long)ii, cdup, rsum);
-    P[D] = part + (double)A.t[9][0];
-    P[D + 1] = (double)n;
-    P[D + 2] = cdup;
-    P[D + 3] = 0.0;
+    P[PL::rhat] = part + (double)A.t[9][0];
+    P[PL::n] = (double)n;
+    P[PL::cdup] = cdup;
+    P[PL::pad] = 0.0;
   }
 }
 
@@ -931,9 +942,7 @@ __device__ __forceinline__ void rows_step(double (&a)[16], double (&b)[32], doub
   const int tb = 31 - t;
   wave_lds_sync();
   const double dj = Pb[J], yj = Pb[32];
-  double ij = __builtin_amdgcn_rcp(dj);            // 1/d_J: v_rcp_f64 + two Newton steps
-  ij = fma(ij, fma(-dj, ij, 1.0), ij);
-  ij = fma(ij, fma(-dj, ij, 1.0), ij);
+  const double ij = rcp_nr2(dj);
   double lt = 0.0;
   if constexpr (J < 16) lt = t > J ? a[J] * ij : 0.0;
   const double lb = tb > J ? b[J] * ij : 0.0;
@@ -1014,7 +1023,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRowsWaves))
     int32_t* __restrict__ coupled_out) {
   static_assert(pair_layout<M>(), "NCF k = 16 (side blocks of 32)");
   constexpr int K = M::K, H2 = K / 2, Ds = M::Ds, D = M::D, GS = Ds * (Ds + 1) / 2, GSP = (GS + 1) & ~1;
-  constexpr int PS = qpro_stride<M>(), PST = 36;   // 36 doubles: the 4 systems' slots in distinct banks
+  constexpr int PST = 36;   // 36 doubles: the 4 systems' slots in distinct banks
+  using PL = QPro<M>;
+  using L = typename M::Rec;
   __shared__ double Pv[2][4 * PST];
   const int lane = threadIdx.x, sys = lane >> 4, t = lane & 15, h = sys >> 1, sd = sys & 1, tb = 31 - t;
   const int64_t q = (int64_t)blockIdx.x * 2 + h;
@@ -1025,7 +1036,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRowsWaves))
   const int32_t uu = okid ? u : 0, ii = okid ? i : 0;
   const int32_t ent = sd ? ii : uu;
   const double* __restrict__ Gb = A.gram[sd] + (int64_t)ent * GSP + t;
-  const double* __restrict__ P = qpro + qc * PS;
+  const double* __restrict__ P = qpro + qc * PL::stride;
   double a[16], b[32];
 #pragma unroll
   for (int s = 0; s <= 32; ++s) {                 // slot s: row t col s | row 31 - t col 32 - s
@@ -1033,7 +1044,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRowsWaves))
     if (s < 16) a[s] = v;
     if (s >= 1) b[32 - s] = v;
   }
-  const double nd = P[D + 1];
+  const double nd = P[PL::n];
   // H_b = (2/n) Gram_b + (wd + damping) I  (every NCF coordinate is decayed); n = 0: the
   // system is garbage and its query writes NaN below
   const double s2n = nd > 0.0 ? 2.0 / nd : 0.0;
@@ -1048,7 +1059,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRowsWaves))
 #pragma unroll
   for (int c = 16; c < 32; ++c)
     if (c == tb) b[c] += lam;
-  double yt = P[sd * Ds + t], yb = P[sd * Ds + tb], dit = 0.0, dib = 0.0;
+  double yt = P[PL::v + sd * Ds + t], yb = P[PL::v + sd * Ds + tb], dit = 0.0, dib = 0.0;
   double* __restrict__ P0 = &Pv[0][sys * PST];
   double* __restrict__ P1 = &Pv[1][sys * PST];
   P0[t] = a[0];
@@ -1058,10 +1069,10 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRowsWaves))
   const double zt = yt * dit, zb = yb * dib;
   double xt = 0.0, xb = 0.0;
   rows_back<31>(a, b, zt, zb, xt, xb, t);
-  // ---- record + x_out (record layout: solve_epilogue); sums over the query's 2 systems ----
+  // ---- record + x_out; sums over the query's 2 systems ----
   // (loaded here, not held across the factorization)
-  const double rh = P[D], cdup = P[D + 2];
-  const double gt = P[sd * Ds + t], gbv = P[sd * Ds + tb];
+  const double rh = P[PL::rhat], cdup = P[PL::cdup];
+  const double gt = P[PL::v + sd * Ds + t], gbv = P[PL::v + sd * Ds + tb];
   // theta at the lane's two coordinates: side 0 [Pm_u | Pg_u], side 1 [Qm_i | Qg_i]
   const double tht = (double)A.t[sd][(int64_t)ent * K + t];
   const double thb = (double)A.t[2 + sd][(int64_t)ent * K + (tb - K)];
@@ -1073,16 +1084,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRowsWaves))
   const int64_t n = (int64_t)nd;
   if (qok && n > 0 && !(cdup > 0.0)) {
     double* __restrict__ R = rec + q * M::R;
-    double* __restrict__ S = R + 4 + sd * M::SB;
+    double* __restrict__ S = L::side(R, sd);
     if (sd == 0 && t == 0) {
-      R[0] = 1.0 / nd;
-      R[1] = cq * A.wd;
-      R[2] = xv;
-      R[3] = rh;
+      R[L::inv_n] = 1.0 / nd;
+      R[L::c_q] = cq * A.wd;
+      R[L::x_v] = xv;
+      R[L::rhat] = rh;
     }
-    S[t] = xt;                                     // x_mlp
-    S[tb] = w3b * xb;                              // W3g * x_gmf
-    if (t == 0) S[2 * K] = (double)(sd ? uu : ii);
+    S[L::x_mlp + t] = xt;
+    S[L::w3g_x_gmf + (tb - K)] = w3b * xb;
+    if (t == 0) S[L::dup_other] = (double)(sd ? uu : ii);
     if (x_out) {
       x_out[q * D + M::ref_index(sd * Ds + t)] = xt;
       x_out[q * D + M::ref_index(sd * Ds + tb)] = xb;
@@ -1092,10 +1103,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kRowsWaves))
       x_out[q * D + sd * Ds + t] = NAN;
       x_out[q * D + sd * Ds + tb] = NAN;
     }
-    if (sd == 0 && t == 0) rec[q * M::R] = NAN;
-  } else if (qok && sd == 0 && t == 0) {          // coupled: the full-D solve finishes it
-    const int slot = atomicAdd(coupled_out, 1);
-    coupled_out[1 + slot] = (int32_t)q;
+    if (sd == 0 && t == 0) rec[q * M::R + M::Rec::inv_n] = NAN;
+  } else if (qok && sd == 0 && t == 0) {
+    coupled_append(coupled_out, q);
   }
 }
 
@@ -1156,9 +1166,7 @@ __device__ __forceinline__ void quad_steps(Quad16& Z, int j) {
   if constexpr (J < 16) {
     constexpr int SJ = J / 4, JJ = J % 4;
     const double dj = quad_bcast<JJ>(Z.a[SJ][J]);
-    double ij = __builtin_amdgcn_rcp(dj);
-    ij = fma(ij, fma(-dj, ij, 1.0), ij);
-    ij = fma(ij, fma(-dj, ij, 1.0), ij);
+    const double ij = rcp_nr2(dj);
     const double yj = quad_bcast<JJ>(Z.y[SJ]), hj = quad_bcast<JJ>(Z.hb[SJ]);
     const double lb = hj * ij;                              // L[16][J]
     double hc[16];
@@ -1239,9 +1247,7 @@ __device__ __forceinline__ void solve_quad_wave(const QueryArgs& A, int64_t Q, d
   Z.hbb = fma(Z.hbb, s2n, A.damping);
   Z.y16 = 1.0;
   quad_steps<0>(Z, j);
-  double i16 = __builtin_amdgcn_rcp(Z.hbb);
-  i16 = fma(i16, fma(-Z.hbb, i16, 1.0), i16);
-  i16 = fma(i16, fma(-Z.hbb, i16, 1.0), i16);
+  const double i16 = rcp_nr2(Z.hbb);
   const double x16 = Z.y16 * i16;
   double z[4];
 #pragma unroll
@@ -1273,27 +1279,28 @@ __device__ __forceinline__ void solve_quad_wave(const QueryArgs& A, int64_t Q, d
       for (int s = 0; s < 4; ++s) x_out[q * D + M::ref_index(sd * Ds + 4 * s + j)] = NAN;
       if (j == 0) x_out[q * D + M::ref_index(sd * Ds + K)] = NAN;
     }
-    if (sd == 0 && j == 0) rec[q * M::R] = NAN;
+    if (sd == 0 && j == 0) rec[q * M::R + M::Rec::inv_n] = NAN;
     return;
   }
   if (cdup > 0.0) return;         // the test pair is a train row: the coupled role's (full D)
   double* __restrict__ R = rec + q * M::R;
+  using L = typename M::Rec;
   if (sd == 0 && j == 0) {
-    R[0] = 1.0 / (double)n;
-    R[1] = cq;
-    R[2] = xg;
-    R[3] = pv + bpair + gb;        // r-hat(u,i)
+    R[L::inv_n] = 1.0 / (double)n;
+    R[L::c_q] = cq;
+    R[L::x_v] = xg;
+    R[L::rhat] = pv + bpair + gb;
   }
-  double* __restrict__ S = R + 4 + sd * M::SB;
+  double* __restrict__ S = L::side(R, sd);
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    S[4 * s + j] = th[s];
-    S[K + 4 * s + j] = Z.x[s];
+    S[L::theta + 4 * s + j] = th[s];
+    S[L::x + 4 * s + j] = Z.x[s];
   }
   if (j == 0) {
-    S[2 * K] = bself + gb;
-    S[2 * K + 1] = x16;
-    S[2 * K + 2] = (double)oth;
+    S[L::bias] = bself + gb;
+    S[L::x_bias] = x16;
+    S[L::dup_other] = (double)oth;
   }
   if (x_out) {
 #pragma unroll
@@ -1426,14 +1433,11 @@ __global__ __launch_bounds__(64) void k_solve_tps(QueryArgs A, int64_t Q, double
   double cdup = 0.0, rsum = 0.0;
   if (active && n > 0)
     A.pairs.lookup((unsigned long long)u * (unsigned long long)A.I + (unsigned long long)i, cdup, rsum);
-  if (active && n > 0 && cdup > 0.0 && side == 0) {
-    const int slot = atomicAdd(coupled, 1);
-    coupled[1 + slot] = (int32_t)q;
-  }
+  if (active && n > 0 && cdup > 0.0 && side == 0) coupled_append(coupled, q);
   if (active && n == 0) {
     if (x_out)
       for (int a = 0; a < Ds; ++a) x_out[q * D + M::ref_index(side * Ds + a)] = NAN;
-    if (side == 0) rec[q * M::R] = NAN;
+    if (side == 0) rec[q * M::R + M::Rec::inv_n] = NAN;
   }
   const bool work = active && n > 0 && cdup == 0.0;
 
@@ -1447,13 +1451,10 @@ __global__ __launch_bounds__(64) void k_solve_tps(QueryArgs A, int64_t Q, double
 
   // right-looking LDL^T: column j holds L[., j], the diagonal holds d
 #pragma unroll
-  // (the diagonal keeps 1/d: v_rcp_f64 + two Newton steps instead of an IEEE division
-  // sequence on the critical path, and the forward solve multiplies by it)
+  // (the diagonal keeps 1/d, rcp_nr2, and the forward solve multiplies by it)
   for (int j = 0; j < Ds; ++j) {
     const double dj = HS(tri(j, j));
-    double inv = __builtin_amdgcn_rcp(dj);
-    inv = fma(inv, fma(-dj, inv, 1.0), inv);
-    inv = fma(inv, fma(-dj, inv, 1.0), inv);
+    const double inv = rcp_nr2(dj);
 #pragma unroll
     for (int r = j + 1; r < Ds; ++r) {
       const double lr = HS(tri(r, j)) * inv;
@@ -1499,21 +1500,22 @@ __global__ __launch_bounds__(64) void k_solve_tps(QueryArgs A, int64_t Q, double
   const double bpair = bself + __shfl_xor(bself, 1);
   if (!work) return;
   double* R = rec + q * M::R;
+  using L = typename M::Rec;
   if (side == 0) {
-    R[0] = 1.0 / (double)n;
-    R[1] = cq;
-    R[2] = xg;
-    R[3] = pv + bpair + gb;        // r-hat(u,i)
+    R[L::inv_n] = 1.0 / (double)n;
+    R[L::c_q] = cq;
+    R[L::x_v] = xg;
+    R[L::rhat] = pv + bpair + gb;
   }
-  double* S = R + 4 + side * M::SB;
+  double* S = L::side(R, side);
 #pragma unroll
   for (int a = 0; a < K; ++a) {
-    S[a] = th[a];
-    S[K + a] = x[a];
+    S[L::theta + a] = th[a];
+    S[L::x + a] = x[a];
   }
-  S[2 * K] = bself + gb;
-  S[2 * K + 1] = x[K];
-  S[2 * K + 2] = (double)oth;
+  S[L::bias] = bself + gb;
+  S[L::x_bias] = x[K];
+  S[L::dup_other] = (double)oth;
   if (x_out)
 #pragma unroll
     for (int a = 0; a < Ds; ++a) x_out[q * D + M::ref_index(side * Ds + a)] = x[a];

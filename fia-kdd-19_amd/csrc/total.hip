@@ -119,18 +119,19 @@ __global__ __launch_bounds__(64) void k_total_agg(TotalArgs A) {
     for (int64_t pp = p; pp < n2 && A.keys[pp] == key; ++pp) {     // ascending query position
       const int64_t q = A.vals[pp];
       const double* __restrict__ Rq = A.rec + q * R;
-      const double inv_n = Rq[0];
+      const double inv_n = Rq[CandHead::inv_n];
 #pragma unroll
       for (int t = 0; t < NA; ++t) {
         const int a = t * 64 + lane;
         if (a >= AS) continue;
         double v;
         if (a == AS - 1) {
-          v = Rq[1];
+          v = Rq[CandHead::c_q];
         } else if constexpr (!M::ncf) {
           v = inv_n * A.x[q * D + (a < K ? sd * K + a : 2 * K + sd)];
         } else {
-          v = inv_n * Rq[2 + (a < K ? sd * K + a : 2 * K + sd * K + (a - K))];
+          // y_user | y_item, w3g_x_pg | w3g_x_qg: the side's half of each pair
+          v = inv_n * Rq[CandHead::head + (a < K ? sd * K + a : 2 * K + sd * K + (a - K))];
         }
         acc[t] += v;
       }
@@ -222,10 +223,11 @@ __global__ __launch_bounds__(kTotalTile) void k_total_rows(TotalArgs A, double* 
       yu = A.agg + (int64_t)sa * AS;
       yi = A.agg + (int64_t)sb * AS;
     } else {
-      coop_dots<KK, true, R, 2 + 2 * KK, 2 + 3 * KK>(valid, a, b, sa, on_u, on_i, A.t[2], A.t[3], A.rec,
-                                                      A.t[8] + KK / 2, rg, sgu, sgi);
-      yu = A.rec + (int64_t)sa * R + 2;
-      yi = A.rec + (int64_t)sa * R + 2 + KK;
+      using L = CandRecNCF<KK>;
+      coop_dots<KK, true, R, L::w3g_x_pg, L::w3g_x_qg>(valid, a, b, sa, on_u, on_i, A.t[2], A.t[3], A.rec,
+                                                        A.t[8] + KK / 2, rg, sgu, sgi);
+      yu = A.rec + (int64_t)sa * R + L::y_user;
+      yi = A.rec + (int64_t)sa * R + L::y_item;
     }
     if (valid) {
       cand_core_ncf<KK>(A, w, a, b, on_u, on_i, yu, yi, z1s + tid, r, s);
@@ -251,7 +253,7 @@ __global__ __launch_bounds__(kTotalTile) void k_total_rows(TotalArgs A, double* 
     }
   }
   if constexpr (!AGG) {
-    if (valid) A.pd[g] = s * A.rec[g * R];
+    if (valid) A.pd[g] = s * A.rec[g * R + CandHead::inv_n];
     return;
   } else {
     double v = 0.0;

@@ -2,12 +2,17 @@
 """Compare the kernels of two sets of gfx950 assembly files (hipcc ... --cuda-device-only -S).
 
     tools/asm_diff.py OLD.s[,OLD2.s...] NEW.s[,NEW2.s...]
+    tools/asm_diff.py OLD_DIR NEW_DIR
+
+Two directories (`make -C fia-kdd-19_amd/csrc asm OBJDIR=<dir>` of two trees writes <dir>/asm) are
+compared unit by unit, a summary line per unit; a unit only one side has counts as a difference.
 
 Per kernel, keyed by its demangled name: the instruction text from the kernel's label to its
 .amdhsa_kernel block (comments dropped, the function number of local labels normalised) and the
 .amdhsa_ resource lines.  Prints the kernels only one side has and the ones that differ; exit
 status 1 if any kernel present on both sides differs.
 """
+import os
 import re
 import subprocess
 import sys
@@ -29,12 +34,11 @@ def kernels(paths):
     return out
 
 
-def main():
-    old, new = kernels(sys.argv[1]), kernels(sys.argv[2])
-    for k in sorted(set(old) - set(new)):
-        print("only in old:", k)
-    for k in sorted(set(new) - set(old)):
-        print("only in new:", k)
+def compare(old_paths, new_paths, unit=""):
+    old, new = kernels(old_paths), kernels(new_paths)
+    only = sorted(set(old) ^ set(new))
+    for k in only:
+        print("only in old:" if k in old else "only in new:", k)
     both = sorted(set(old) & set(new))
     bad = 0
     for k in both:
@@ -47,8 +51,23 @@ def main():
                     print("   ", a, "->", b)
             if ot != nt:
                 print("    instruction text: %d -> %d lines" % (len(ot), len(nt)))
-    print("%d kernels on both sides, %d identical, %d differ" % (len(both), len(both) - bad, bad))
-    return 1 if bad else 0
+    print("%s%d kernels on both sides, %d identical, %d differ" % (unit, len(both), len(both) - bad, bad))
+    return bad, len(only)
+
+
+def main():
+    a, b = sys.argv[1], sys.argv[2]
+    if not (os.path.isdir(a) and os.path.isdir(b)):
+        return 1 if compare(a, b)[0] else 0
+    units = [sorted(f for f in os.listdir(d) if f.endswith(".s")) for d in (a, b)]
+    status = 0
+    for f in sorted(set(units[0]) ^ set(units[1])):
+        print("%s: only in %s" % (f, a if f in units[0] else b))
+        status = 1
+    for f in sorted(set(units[0]) & set(units[1])):
+        bad, only = compare(os.path.join(a, f), os.path.join(b, f), f + ": ")
+        status |= 1 if bad or only else 0
+    return status
 
 
 if __name__ == "__main__":
