@@ -40,18 +40,30 @@ constexpr int kGsSlice = 256;           // longest Gram-stream segment (longer l
                                         // <= 511: a segment's count rides in 9 bits of its descriptor)
 constexpr int kGsTarget = 8;            // sub-batches per Gram-stream wave (a range closes at >= this)
 // (ml-1m-ex same-box A/B, ms per step: target 16 0.1460-0.1461; 8 0.1446-0.1448; 32 0.1442-0.1453;
-//  slices of 128 0.1483; at most 8 segments per range 0.1481)
+//  slices of 128 0.1483; at most 8 segments per range 0.1481.  With 4-wave team workgroups, one
+//  batch in flight: target 8 0.1206-0.1215; 12 0.1224-0.1230; 16 0.1257-0.1259; 8 waves
+//  0.1252-0.1253; short teams two slices per wave 0.1225-0.1229 -- profiles/gram_teams.md)
 constexpr uint32_t kGsNoRow = 0x7fffff00u;   // Gram-stream row offset of no rating: outside any
                                              // table's buffer range, even + a lane's column bytes
 constexpr int kGsRing = 8;              // gathered sub-batches in the kernel's register ring
 constexpr int kGsMaxSub = 48;           // most sub-batches of one wave's range (a multiple of kGsRing)
 constexpr int kGsMaxSeg = 4;            // most segments (Grams) of one wave's range: staged in LDS,
                                         // stored when the range is done
+constexpr int kGsWaves = 4;             // waves (ranges) of a Gram-stream workgroup
+constexpr int kGsTeamPer = kGsMaxSub / (kGsSlice / kGsSub);   // most slices of a team in one wave (3)
+constexpr int kGsTeamSlices = kGsWaves * kGsTeamPer;   // a team's reach: the longest list (in slices)
+                                        // whose slices one workgroup sums in LDS; longer: gscomb
+constexpr int kGsTeamMinPer = 1;         // fewest slices per wave of a team (1: a short team is spread
+                                        // one slice per wave)
+constexpr uint32_t kGsTeamBit = 1u << 22;   // descriptor `out`: a team slice {slice << 8 | slices << 3 | per}
 constexpr int kMfmaQB = 16;             // queries per MF k in {32, 64} MFMA scoring work item
 constexpr int kMfmaCPI = 4;             // list chunks per MFMA scoring work item
 constexpr int kWgBlocks = 4;            // query blocks (one per wave) sharing a workgroup's gathered rows
 constexpr int kQueryBlock = 8;           // queries per entity-shared scoring work item (small k; 16 measured no better)
 static_assert(kGsSlice < 512, "a Gram-stream segment's count rides in 9 bits of its descriptor (out >> 23)");
+static_assert(kGsSlice % kGsSub == 0 && kGsTeamPer >= 1 && kGsTeamPer <= kGsMaxSeg && kGsTeamPer < 8 &&
+                  kGsTeamSlices < 32,
+              "a team wave stages its slices from segment 0; slice and count ride in 5 bits each, per in 3");
 
 // Device buffer with grow-on-demand capacity (never shrinks), allocated from the
 // device's stream-ordered pool on the context's stream: growing a buffer frees the old
@@ -126,8 +138,13 @@ struct Index {
   // | last of its segment << 5 | side << 6 | dummy << 7 | entity << 8; out, on a segment's last
   // sub-batch: its rating count << 23 | partial slot + 1, 0 = the entity's own Gram), the byte
   // offsets of their other-side rows in stream order (kGsSub per sub-batch, kGsNoRow past a
-  // list's end), and the first descriptor of every wave's range (whole lists up to kGsSlice
-  // ratings, longer lists in kGsSlice slices whose partial Grams gscomb sums in slot order)
+  // list's end), and the first descriptor of every wave's range, kGsWaves ranges to a workgroup
+  // (n_gsw is a multiple of it).  Whole lists up to kGsSlice ratings; a longer list in kGsSlice
+  // slices: up to kGsTeamSlices of them as a team, out = count << 23 | kGsTeamBit | slice << 8 |
+  // slices << 3 | slices per wave, all in consecutive waves of one workgroup, which sums them
+  // in LDS in slice order.  gscomb {entity, first slot, slots, 0} and n_gsslots cover only the
+  // lists beyond that reach: their slices go to partial slots (Ctx::gpart) and k_gram_combine
+  // sums them in slot order; both are empty where no list is that long
   DevBuf gsdesc, gsids, gswave, gscomb[2];
   int64_t n_gsw = 0, n_gsdesc = 0, n_gscomb[2] = {0, 0}, n_gsslots[2] = {0, 0};
   uint64_t gs_version = ~0ull;

@@ -11,8 +11,8 @@ constexpr int kRsrcWord3 = 0x00020000;
 
 // ------------------------------------------------------------------------------------
 // The lists of both sides are cut into sub-batches of 16 ratings (build_gram_stream): a wave
-// walks the sub-batches of its range -- whole short lists one after another, or one
-// 256-rating slice of a long list -- with one v_mfma_f64_16x16x4_f64 per row-quad (4 per
+// walks the sub-batches of its range -- whole short lists one after another, or up to three
+// 256-rating slices of a long list -- with one v_mfma_f64_16x16x4_f64 per row-quad (4 per
 // sub-batch: a list costs ceil(len / 4) MFMAs, not a padded 64-row batch), and flushes an
 // entity's Gram when its last sub-batch is in.  The range's row offsets go to LDS once (stream
 // order, quad-transposed: one 16-B LDS read gives a row group its 4 quads' row offsets, and no
@@ -25,39 +25,48 @@ constexpr int kRsrcWord3 = 0x00020000;
 // the packed triangle (+ the bias row: column sums, the count) in LDS and writes it as 16-B
 // stores.  fia_prepare_for marks (MARK): the sub-batches of unmarked entities gather past every
 // table's range, skip their MFMAs and end no segment.
+// A workgroup is kGsWaves waves, each with a range, a stage[] and a sids[] of its own.  A list
+// of 2 .. kGsTeamSlices slices is a team: its slices are the only segments of consecutive waves
+// of ONE workgroup (`per` to a wave, from the wave's segment 0), and after the workgroup's one
+// barrier the wave that holds slice 0 sums the staged slices in slice order from 0.0 -- the
+// order and the bits of k_gram_combine -- and writes the list's Gram.  Longer lists write their
+// slices to partial slots for k_gram_combine as before.
 // Lane map (f64 16x16x4): lane l supplies G[l >> 4][l & 15] of the row-quad as both A (= G^T)
 // and B; C register r = C[(l >> 4) + 4 r][l & 15].
 // ------------------------------------------------------------------------------------
 template <class M, bool MARK>
-__global__ __launch_bounds__(64) void k_gram_mf_stream(GramStreamArgs G) {
+__global__ __launch_bounds__(64 * kGsWaves) void k_gram_mf_stream(GramStreamArgs G) {
   static_assert(!M::ncf && M::K <= 16, "MF k <= 16");
   constexpr int K = M::K, Ds = M::Ds, GS = Ds * (Ds + 1) / 2, GSP = (GS + 1) & ~1;
   static_assert(kGsRing == 8 && kGsMaxSub % kGsRing == 0 && kGsMaxSub + kGsRing <= 64, "ring of 8");
-  __shared__ __attribute__((aligned(16))) double stage[kGsMaxSeg][GSP];
-  __shared__ uint4 sids[kGsMaxSub * 4];     // [sub-batch][row group] -> the group's 4 row offsets
-  const int64_t w = blockIdx.x;
-  if (w >= G.n_waves) return;
-  const int d0 = G.wave[w], nd = G.wave[w + 1] - d0;     // a multiple of kGsRing, <= kGsMaxSub
-  const int lane = threadIdx.x;
+  __shared__ __attribute__((aligned(16))) double stage_all[kGsWaves][kGsMaxSeg][GSP];
+  __shared__ uint4 sids_all[kGsWaves][kGsMaxSub * 4];     // [sub-batch][row group] -> the group's 4 row offsets
+  const int wid = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  double (*const stage)[GSP] = stage_all[wid];
+  uint4* const sids = sids_all[wid];
+  const int64_t w = (int64_t)blockIdx.x * kGsWaves + wid;     // n_waves is a multiple of kGsWaves
+  const int d0 = G.wave[w], nd0 = G.wave[w + 1] - d0;    // a multiple of kGsRing, <= kGsMaxSub
+  const int lane = threadIdx.x & 63;
   const int col = lane & 15, grp = lane >> 4;
   // the range's descriptors, one per lane, as wave masks: skipped (padding dummies; MARK:
   // unmarked entities), last of a segment, side 1
-  const int2 dv = lane < nd ? G.desc[d0 + lane] : int2{1 << 7, 0};
+  const int2 dv = lane < nd0 ? G.desc[d0 + lane] : int2{1 << 7, 0};
   bool sk = (dv.x >> 7) & 1;
   // (moff picked by a select: a lane-indexed kernel-argument array would go through scratch)
   if constexpr (MARK) sk = sk || !G.mark[((dv.x >> 6) & 1 ? G.moff[1] : G.moff[0]) + (dv.x >> 8)];
   const uint64_t skipm = __ballot(sk), lastm = __ballot((dv.x >> 5) & 1), sidem = __ballot((dv.x >> 6) & 1);
-  if (MARK && skipm == ~0ull) return;     // no marked entity in the range
-  {
+  // nothing to do in the range (a workgroup's unused wave; MARK: no marked entity): no gather, no
+  // loop trip, no segment -- but the wave still meets the others at the barrier
+  const int nd = skipm == ~0ull ? 0 : nd0;
+  if (nd > 0) {
     const uint4* __restrict__ src = reinterpret_cast<const uint4*>(G.ids) + (int64_t)d0 * 4;
-    uint4 tmp[kGsMaxSub * 4 / 64];
-#pragma unroll
-    for (int r = 0; r < kGsMaxSub * 4 / 64; ++r) {
-      const int i = r * 64 + lane;
-      tmp[r] = src[i < nd * 4 ? i : 0];
-    }
-#pragma unroll
-    for (int r = 0; r < kGsMaxSub * 4 / 64; ++r) sids[r * 64 + lane] = tmp[r];
+    // (three named words: an array here, under the branch, was left in scratch)
+    static_assert(kGsMaxSub * 4 == 3 * 64, "three 16-B words per lane");
+    const int n4 = nd * 4;
+    const uint4 t0 = src[lane < n4 ? lane : 0], t1 = src[64 + lane < n4 ? 64 + lane : 0], t2 = src[128 + lane < n4 ? 128 + lane : 0];
+    sids[lane] = t0;
+    sids[64 + lane] = t1;
+    sids[128 + lane] = t2;
     wave_lds_sync();
   }
   const __amdgpu_buffer_rsrc_t rs0 =
@@ -127,8 +136,10 @@ __global__ __launch_bounds__(64) void k_gram_mf_stream(GramStreamArgs G) {
   // the top bit, see rows())
   constexpr int AH = kGsRing - 2;
   float r[kGsRing][4];
+  if (nd > 0) {
 #pragma unroll
-  for (int j = 0; j < AH; ++j) rows(j, r[j]);
+    for (int j = 0; j < AH; ++j) rows(j, r[j]);
+  }
   for (int t = 0; t < nd; t += kGsRing) {
 #pragma unroll
     for (int j = 0; j < kGsRing; ++j) {
@@ -137,16 +148,40 @@ __global__ __launch_bounds__(64) void k_gram_mf_stream(GramStreamArgs G) {
     }
   }
   // the range's Grams, in segment order: segment k ends at the k-th descriptor that is the last
-  // of a segment and not skipped
-  wave_lds_sync();
+  // of a segment and not skipped.  The barrier is the workgroup's only one: behind it a team's
+  // slices are all staged
+  __syncthreads();
   uint64_t ends = lastm & ~skipm;
   for (int k = 0; k < nseg; ++k) {
     const int t = (int)__builtin_ctzll(ends);
     ends &= ends - 1;
     const int meta = __builtin_amdgcn_readlane(dv.x, t);
     const uint32_t out = (uint32_t)__builtin_amdgcn_readlane(dv.y, t);
-    const int sd = (meta >> 6) & 1, e = meta >> 8, slot = (int)(out & 0x7fffffu) - 1;
-    double* __restrict__ o = slot < 0 ? G.gram[sd] + (int64_t)e * GSP : G.part[sd] + (int64_t)slot * GSP;
+    const int sd = (meta >> 6) & 1, e = meta >> 8;
+    // (picked by selects: a kernel-argument array indexed by sd would go through scratch)
+    double* const gram_e = (sd ? G.gram[1] : G.gram[0]) + (int64_t)e * GSP;
+    if (out & kGsTeamBit) {
+      // a team slice {slice << 8 | slices << 3 | per}: slice 0's wave sums the list's slices,
+      // `per` in each wave from this one on, in slice order from 0.0
+      if ((out >> 8) & 31) continue;
+      const int ns = (int)(out >> 3) & 31, per = (int)out & 7;
+      double* __restrict__ o = gram_e;
+#pragma unroll
+      for (int b = 0; b < GSP; b += 128)
+        if (b + 2 * lane < GSP) {
+          double2 a = {0.0, 0.0};
+          for (int j = 0, ww = wid, kk = 0; j < ns; ++j) {
+            const double2 v = *reinterpret_cast<const double2*>(&stage_all[ww][kk][b + 2 * lane]);
+            a.x += v.x;
+            a.y += v.y;
+            if (++kk == per) kk = 0, ++ww;
+          }
+          *reinterpret_cast<double2*>(o + b + 2 * lane) = a;
+        }
+      continue;
+    }
+    const int slot = (int)(out & 0x7fffffu) - 1;
+    double* __restrict__ o = slot < 0 ? gram_e : (sd ? G.part[1] : G.part[0]) + (int64_t)slot * GSP;
 #pragma unroll
     for (int b = 0; b < GSP; b += 128)
       if (b + 2 * lane < GSP)
@@ -158,7 +193,8 @@ __global__ __launch_bounds__(64) void k_gram_mf_stream(GramStreamArgs G) {
 
 hipError_t launch_gram_mf_stream(int k, const GramStreamArgs& G, hipStream_t s) {
   if (G.n_waves <= 0) return hipSuccess;
-  const dim3 grid((unsigned)G.n_waves), blk(64);
+  if (G.n_waves % kGsWaves) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(G.n_waves / kGsWaves)), blk(64 * kGsWaves);
   if (k == 16) {
     if (G.mark) hipLaunchKernelGGL((k_gram_mf_stream<MFm<16>, true>), grid, blk, 0, s, G);
     else hipLaunchKernelGGL((k_gram_mf_stream<MFm<16>, false>), grid, blk, 0, s, G);

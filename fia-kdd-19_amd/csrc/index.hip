@@ -317,7 +317,17 @@ hipError_t build_gram_stream(fia_ctx* c, int k, hipStream_t s) {
     int side;
     int32_t e, start, slot;
   };
+  struct Team {
+    int64_t len;
+    int side;
+    int32_t e, nit;
+  };
+  struct Range {   // one wave's descriptors and the list positions of their first ratings
+    std::vector<int2> d;
+    std::vector<int32_t> p;
+  };
   std::vector<Seg> segs;
+  std::vector<Team> teams;
   std::vector<int32_t> comb[2];
   for (int sd = 0; sd < 2; ++sd) {
     const std::vector<int64_t>& hptr = X.hptr[sd];
@@ -329,42 +339,94 @@ hipError_t build_gram_stream(fia_ctx* c, int k, hipStream_t s) {
         continue;
       }
       const int64_t nit = (len + kGsSlice - 1) / kGsSlice;
+      if (nit <= kGsTeamSlices) {   // summed by its workgroup
+        teams.push_back({len, sd, e, (int32_t)nit});
+        continue;
+      }
+      // beyond a team's reach: partial slots, summed by k_gram_combine
       comb[sd].insert(comb[sd].end(), {e, slots, (int32_t)nit, 0});
       for (int64_t t = 0; t < nit; ++t)
         segs.push_back({std::min<int64_t>(kGsSlice, len - t * kGsSlice), sd, e, (int32_t)(t * kGsSlice), slots++});
     }
+    if ((uint32_t)slots >= kGsTeamBit) return hipErrorInvalidValue;   // slot + 1 stays below the team bit
     X.n_gsslots[sd] = slots;
   }
-  // longest segments first (both sides merged): the slices of the long lists start early
+  // longest first (both sides merged): the deep teams, then the slices of the lists beyond a
+  // team's reach, then the whole lists
+  std::stable_sort(teams.begin(), teams.end(), [](const Team& a, const Team& b) { return a.len > b.len; });
   std::stable_sort(segs.begin(), segs.end(), [](const Seg& a, const Seg& b) { return a.len > b.len; });
-  std::vector<int2> desc;
-  std::vector<int32_t> pos, wave{0};
-  int cur = 0, nseg = 0;
-  auto close_wave = [&]() {
-    while (cur % kGsRing) {   // a multiple of the ring per wave (one ring turn per loop trip)
-      desc.push_back(int2{1 << 7, -1});
-      pos.push_back(0);
-      ++cur;
-    }
-    wave.push_back((int32_t)desc.size());
-    cur = 0;
-    nseg = 0;
-  };
-  for (const Seg& g : segs) {
+  // a segment's sub-batches appended to a range; `out` rides on the last one
+  auto emit = [&](Range& r, const Seg& g, uint32_t out_low) {
     const int nsb = g.len == 0 ? 1 : (int)((g.len + kGsSub - 1) / kGsSub);
-    if (cur > 0 && cur + nsb > kGsMaxSub - kGsRing) close_wave();
     for (int t = 0; t < nsb; ++t) {
       const int valid = (int)std::min<int64_t>(kGsSub, g.len - (int64_t)t * kGsSub);
       const bool last = t == nsb - 1;
       const int meta = (valid < 0 ? 0 : valid) | (last ? 1 << 5 : 0) | (g.side << 6) | (g.e << 8);
-      const uint32_t out = last ? ((uint32_t)g.len << 23) | (uint32_t)(g.slot + 1) : 0u;
-      desc.push_back(int2{meta, (int)out});
-      pos.push_back((int32_t)(X.hptr[g.side][(size_t)g.e] + g.start + (int64_t)t * kGsSub));
+      const uint32_t out = last ? ((uint32_t)g.len << 23) | out_low : 0u;
+      r.d.push_back(int2{meta, (int)out});
+      r.p.push_back((int32_t)(X.hptr[g.side][(size_t)g.e] + g.start + (int64_t)t * kGsSub));
     }
-    cur += nsb;
-    if (cur >= kGsTarget || ++nseg >= kGsMaxSeg) close_wave();
+    return nsb;
+  };
+  auto close = [&](Range& r) {
+    while (r.d.size() % kGsRing) {   // a multiple of the ring per wave (one ring turn per loop trip)
+      r.d.push_back(int2{1 << 7, -1});
+      r.p.push_back(0);
+    }
+  };
+  // workgroups of kGsWaves ranges.  A team's slices are the only segments of consecutive ranges
+  // of one workgroup, `per` to a range (one while the waves last, up to kGsTeamPer); a team that
+  // does not fit behind the last one opens a new workgroup
+  std::vector<std::vector<Range>> wgs;
+  for (const Team& tm : teams) {
+    const int per = std::max(kGsTeamMinPer, (tm.nit + kGsWaves - 1) / kGsWaves), nw = (tm.nit + per - 1) / per;
+    if (wgs.empty() || (int)wgs.back().size() + nw > kGsWaves) wgs.emplace_back();
+    std::vector<Range>& wg = wgs.back();
+    for (int32_t j = 0; j < tm.nit; ++j) {
+      if (j % per == 0) wg.emplace_back();
+      const Seg g{std::min<int64_t>(kGsSlice, tm.len - (int64_t)j * kGsSlice), tm.side, tm.e, j * kGsSlice, -1};
+      emit(wg.back(), g, kGsTeamBit | (uint32_t)j << 8 | (uint32_t)tm.nit << 3 | (uint32_t)per);
+      if (j % per == per - 1 || j == tm.nit - 1) close(wg.back());
+    }
   }
-  if (cur > 0) close_wave();
+  // the other segments packed into ranges as before; the ranges fill the waves the teams left
+  // free, first workgroup first, then workgroups of their own
+  size_t fill = 0;
+  auto place = [&](Range&& r) {
+    close(r);
+    while (fill < wgs.size() && (int)wgs[fill].size() >= kGsWaves) ++fill;
+    if (fill == wgs.size()) wgs.emplace_back();
+    wgs[fill].push_back(std::move(r));
+  };
+  {
+    Range r;
+    int cur = 0, nseg = 0;
+    for (const Seg& g : segs) {
+      const int nsb = g.len == 0 ? 1 : (int)((g.len + kGsSub - 1) / kGsSub);
+      if (cur > 0 && cur + nsb > kGsMaxSub - kGsRing) {
+        place(std::move(r));
+        r = Range{};
+        cur = nseg = 0;
+      }
+      cur += emit(r, g, (uint32_t)(g.slot + 1));
+      if (cur >= kGsTarget || ++nseg >= kGsMaxSeg) {
+        place(std::move(r));
+        r = Range{};
+        cur = nseg = 0;
+      }
+    }
+    if (cur > 0) place(std::move(r));
+  }
+  std::vector<int2> desc;
+  std::vector<int32_t> pos, wave{0};
+  for (std::vector<Range>& wg : wgs) {
+    wg.resize(kGsWaves);   // a wave without a range walks nothing
+    for (const Range& r : wg) {
+      desc.insert(desc.end(), r.d.begin(), r.d.end());
+      pos.insert(pos.end(), r.p.begin(), r.p.end());
+      wave.push_back((int32_t)desc.size());
+    }
+  }
   const int64_t nd = (int64_t)desc.size();
   X.n_gsdesc = nd;
   X.n_gsw = (int64_t)wave.size() - 1;

@@ -71,9 +71,10 @@ hipError_t prepare_impl(fia_ctx* c, hipStream_t s, const uint8_t* mark) {
   }
   constexpr int GSP = (GS + 1) & ~1;
   const Index& X = c->idx;
-  // MF k <= 16: the Gram stream (both sides, one launch), then the partial slices combined.  It
-  // cuts its own sub-batches (build_gram_stream) and needs neither the slice lists of the
-  // per-slice kernels nor their partial-Gram slots
+  // MF k <= 16: the Gram stream (both sides, one launch).  It cuts its own sub-batches
+  // (build_gram_stream) and needs neither the slice lists of the per-slice kernels nor their
+  // partial-Gram slots; a split list is summed by the workgroup that holds its slices, and only
+  // lists beyond a team's reach leave partial slices for the combine (none: no second launch)
   if (use_gram_stream<M>(n_ent)) {
     FIA_HIP_TRY(build_gram_stream(c, K, s));
     for (int sd = 0; sd < 2; ++sd)
