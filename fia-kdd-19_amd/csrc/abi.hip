@@ -678,6 +678,43 @@ int fia_query_batch_newton(fia_ctx* c, int64_t Q, const int32_t* qu, const int32
   })
 }
 
+int fia_score_candidates_newton(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi,
+                                const int64_t* cand_offsets, int64_t total_cand, const int32_t* cand_user,
+                                const int32_t* cand_item, const float* cand_rating, double* newton_add, int K,
+                                int64_t* topk_pos, double* topk_val, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
+    // (2 Q + 3 sort keys in 32 bits)
+    if (Q < 0 || Q > FIA_CAND_NEWTON_MAX_QUERIES) return fail(c, FIA_ERR_INVALID, "num_queries out of range [0, 2^30]");
+    if (total_cand < 0) return fail(c, FIA_ERR_INVALID, "total_cand < 0");
+    // a candidate's position is kept in 32 bits by the partition and by the top-K selection
+    if (total_cand > FIA_CAND_MAX_TOTAL)
+      return fail(c, FIA_ERR_INVALID, "total_cand > 2^31 - 1: split the batch");
+    if (K < 0 || K > FIA_MAX_TOPK) return fail(c, FIA_ERR_INVALID, "K must be in [0, FIA_MAX_TOPK]");
+    if (Q > 0 && (!qu || !qi || !cand_offsets)) return fail(c, FIA_ERR_INVALID, "null query array");
+    if (total_cand > 0 && (!cand_user || !cand_item || !cand_rating))
+      return fail(c, FIA_ERR_INVALID, "null candidate array");
+    if (K > 0 && (!topk_pos || !topk_val)) return fail(c, FIA_ERR_INVALID, "null top-K output");
+    if (!newton_add && K == 0) return fail(c, FIA_ERR_INVALID, "no output requested (newton_add, top-K)");
+    if (Q == 0) return FIA_OK;
+    if (!fia::newton_supported(c->p.model, c->p.k))
+      return fail(c, FIA_ERR_UNSUPPORTED,
+                  "fia_score_candidates_newton is built for MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32}; the "
+                  "large-k models are not supported yet");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_score_candidates_newton"); rc != FIA_OK) return rc;
+    // the Gram caches of a pending small-k pass are read: join it, as fia_query_batch_newton does
+    if (hipError_t es = fia::join_prepare(c, s); es != hipSuccess)
+      return hip_fail(c, es, "fia_score_candidates_newton");
+    hipError_t e = fia::score_candidates_newton(c, Q, qu, qi, cand_offsets, total_cand, cand_user, cand_item,
+                                                cand_rating, newton_add, K, topk_pos, topk_val, s);
+    if (e != hipSuccess) return hip_fail(c, e, "fia_score_candidates_newton");
+    return FIA_OK;
+  })
+}
+
 int fia_set_profiling(fia_ctx* c, int phase_mask) {
   if (!c) return FIA_ERR_INVALID;
   c->profiling = (unsigned)phase_mask & ((1u << FIA_NUM_PHASES) - 1u);

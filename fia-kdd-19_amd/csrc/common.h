@@ -507,6 +507,12 @@ hipError_t score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int3
                             const int32_t* cand_item, const float* cand_rating, double* influence, int K,
                             int64_t* topk_pos, double* topk_val, hipStream_t s);
 
+// the per-query merge of the slots tile + q that the (tile, query) segments of tiles of kCandTile
+// candidates wrote into c->cand_pos / c->cand_val (score_cand.hip's k_cand_merge, for a caller in
+// another unit)
+hipError_t launch_cand_merge(fia_ctx* c, int64_t Q, int64_t total, const int64_t* cand_offsets, int K,
+                             int64_t* topk_pos, double* topk_val, hipStream_t s);
+
 // fia_total_influence (total.hip): the scatter-add of fia_query_batch_x's influence by train
 // row, computed from per-entity aggregates of the queries; scratch: c->rec, c->cand_pos,
 // c->cand_val and the t* buffers
@@ -554,6 +560,16 @@ bool newton_supported(int model, int k);
 hipError_t query_newton(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* offsets,
                         int64_t total_rel, int32_t* rel_idx, double* newton, int K, int64_t* topk_pos,
                         int64_t* topk_idx, double* topk_val, hipStream_t s);
+
+// fia_score_candidates_newton (cand_newton.hip): hypothetical ratings with their own curvature in
+// the system, one factorisation per query and a quadratic form per candidate; the sizes of
+// newton_supported; scratch: c->rec (the per-query records, in launches of bounded size), c->tkeys,
+// c->tvals, c->tsort (the partition by (query, side)), c->tslot, c->tword, c->d1tab, c->cand_pos,
+// c->cand_val, and c->gxq for the values when `newton_add` is NULL
+hipError_t score_candidates_newton(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi,
+                                   const int64_t* cand_offsets, int64_t total_cand, const int32_t* cand_user,
+                                   const int32_t* cand_item, const float* cand_rating, double* newton_add, int K,
+                                   int64_t* topk_pos, double* topk_val, hipStream_t s);
 
 // phase event helpers (no-ops unless profiling)
 void phase_begin(fia_ctx* c, int phase, hipStream_t s);

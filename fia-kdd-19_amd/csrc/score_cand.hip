@@ -261,6 +261,13 @@ hipError_t score_impl(fia_ctx* c, const CandArgs& A0, double* influence, int K, 
 
 }  // namespace
 
+hipError_t launch_cand_merge(fia_ctx* c, int64_t Q, int64_t total, const int64_t* cand_offsets, int K,
+                             int64_t* topk_pos, double* topk_val, hipStream_t s) {
+  hipLaunchKernelGGL(k_cand_merge, dim3((unsigned)(Q < kCandRecGrid ? Q : kCandRecGrid)), dim3(256), 0, s, Q, total,
+                     cand_offsets, K, c->cand_pos.as<int32_t>(), c->cand_val.as<double>(), topk_pos, topk_val);
+  return hipGetLastError();
+}
+
 hipError_t score_candidates(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const double* x,
                             const int64_t* cand_offsets, int64_t total_cand, const int32_t* cand_user,
                             const int32_t* cand_item, const float* cand_rating, double* influence, int K,

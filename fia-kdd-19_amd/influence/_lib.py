@@ -43,6 +43,8 @@ SIGNATURES = {
     "fia_group_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P]),
     "fia_self_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
     "fia_query_batch_newton": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
+    "fia_score_candidates_newton": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P,
+                                                   _P]),
     "fia_num_params": (ctypes.c_int, [_P]),
     "fia_set_profiling": (ctypes.c_int, [_P, ctypes.c_int]),
     "fia_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I64)]),
@@ -387,6 +389,44 @@ class Context(object):
                                              _ptr(newton), int(K), _ptr(topk_pos), _ptr(topk_idx), _ptr(topk_val),
                                              _stream())
         self._check(rc, "fia_query_batch_newton")
+
+    def score_candidates_newton(self, qu, qi, cand_offsets, total, cand_user, cand_item, cand_rating,
+                                newton_add=None, K=0, topk_pos=None, topk_val=None):
+        """fia_score_candidates_newton: the Newton-corrected influence of hypothetical ratings
+        (cand_user, cand_item, cand_rating), candidates cand_offsets[q]:cand_offsets[q+1] belonging
+        to query q -- score_candidates with the candidate's own curvature in the system, one
+        factorisation per query (no x is passed) -- into newton_add (float64 [total]) and, with K,
+        the K candidates of largest |newton_add| per query (topk_pos int64 [Q * K] positions inside
+        the query's list, topk_val float64 [Q * K])."""
+        import torch
+        for t, name in ((qu, "qu"), (qi, "qi"), (cand_user, "cand_user"), (cand_item, "cand_item")):
+            self._need_int32(t, name)
+        if qi.numel() != qu.numel():
+            raise ValueError("qu and qi must have the same length")
+        Q = qu.numel()
+        if cand_rating.dtype != torch.float32:
+            raise TypeError("cand_rating must be a torch.float32 tensor (got %s)" % cand_rating.dtype)
+        if cand_offsets.dtype != torch.int64 or cand_offsets.numel() != Q + 1:
+            raise TypeError("cand_offsets must be a torch.int64 tensor of Q + 1 values")
+        for t, name in ((newton_add, "newton_add"), (topk_val, "topk_val")):
+            if t is not None and t.dtype != torch.float64:
+                raise TypeError("%s must be a torch.float64 tensor" % name)
+        if topk_pos is not None and topk_pos.dtype != torch.int64:
+            raise TypeError("topk_pos must be a torch.int64 tensor")
+        for t, name in ((qu, "qu"), (qi, "qi"), (cand_offsets, "cand_offsets"), (cand_user, "cand_user"),
+                        (cand_item, "cand_item"), (cand_rating, "cand_rating"), (newton_add, "newton_add"),
+                        (topk_pos, "topk_pos"), (topk_val, "topk_val")):
+            if t is not None and not (t.is_cuda and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous device (cuda) tensor" % name)
+        if min(cand_user.numel(), cand_item.numel(), cand_rating.numel()) < total or (
+                newton_add is not None and newton_add.numel() < total):
+            raise ValueError("candidate arrays hold fewer than total = %d values" % total)
+        if K and (topk_pos is None or topk_val is None or min(topk_pos.numel(), topk_val.numel()) < Q * K):
+            raise ValueError("top-K outputs must hold Q * K values")
+        rc = self.lib.fia_score_candidates_newton(self.h, Q, _ptr(qu), _ptr(qi), _ptr(cand_offsets), int(total),
+                                                  _ptr(cand_user), _ptr(cand_item), _ptr(cand_rating),
+                                                  _ptr(newton_add), int(K), _ptr(topk_pos), _ptr(topk_val), _stream())
+        self._check(rc, "fia_score_candidates_newton")
 
     # ---- profiling ----
     def set_profiling(self, on, phases=None):

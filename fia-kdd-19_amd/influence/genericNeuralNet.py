@@ -460,6 +460,52 @@ class GenericNeuralNet(object):
             out["topk_val"] = tv[:Q * K].cpu().numpy().reshape(Q, K)
         return out
 
+    def get_candidate_newton_batch(self, test_indices, cand_offsets, X, Y, K=0, full=True):
+        """Newton-corrected influence of HYPOTHETICAL ratings on the predictions of many test
+        ratings (one fia_score_candidates_newton call): get_candidate_influence_batch with the
+        candidate's own curvature in the system,
+
+            newton_c = v . (H + H_c)^-1 b_c,   H_c = (2 g_c g_c^T + 2 e_c C [a == u and b == i] + wd diag(M)) / n_q,
+                                               b_c = (2 e_c g_c + wd M theta_t) / n_q
+
+        (include/fia.h) -- one Newton step of the objective with the rating added; the predicted
+        change of r-hat(u, i) is -newton_c.  Candidates cand_offsets[q]:cand_offsets[q+1] -- rows of
+        X [M, 2] (user, item) with ratings Y [M] -- belong to test rating test_indices[q].  There is
+        no inverse_hvp: the call factorises each query's system itself.  Shapes, offsets, id ranges
+        and K (an integer in [0, FIA_MAX_TOPK]; full=False needs K > 0) are checked on the host
+        (ValueError) before any GPU call.  Returns dict(cand_offsets, newton, topk_pos, topk_val) as
+        numpy arrays (newton only with full, top-K only with K: positions inside each query's
+        candidate list, -1 / NaN where the list is shorter than K).  The large-k models raise
+        FIAError (unsupported)."""
+        off, cu, ci, cy = self._checked_candidates(len(test_indices), cand_offsets, X, Y)
+        if isinstance(K, bool) or int(K) != K or not 0 <= int(K) <= _lib.FIA_MAX_TOPK:
+            raise ValueError("K must be in [0, %d]" % _lib.FIA_MAX_TOPK)
+        K = int(K)
+        if not full and K == 0:
+            raise ValueError("nothing to return: full=False needs K > 0")
+        import torch
+        qu, qi = self._query_tensors(test_indices)
+        Q = qu.numel()
+        dev = self.ctx.torch_device
+        # (the count rejects query ids out of range and queries outside a prepare_for cover)
+        self.ctx.count_related(qu, qi)
+        m = cy.size
+        d_off = torch.from_numpy(off).to(dev)
+        d_cu = torch.from_numpy(cu).to(dev) if m else torch.empty(1, dtype=torch.int32, device=dev)
+        d_ci = torch.from_numpy(ci).to(dev) if m else torch.empty(1, dtype=torch.int32, device=dev)
+        d_cy = torch.from_numpy(cy).to(dev) if m else torch.empty(1, dtype=torch.float32, device=dev)
+        nw = torch.empty(max(m, 1), dtype=torch.float64, device=dev) if full else None
+        tp = torch.empty(max(Q * K, 1), dtype=torch.int64, device=dev) if K else None
+        tv = torch.empty(max(Q * K, 1), dtype=torch.float64, device=dev) if K else None
+        self.ctx.score_candidates_newton(qu, qi, d_off, m, d_cu, d_ci, d_cy, nw, K, tp, tv)
+        out = dict(cand_offsets=off)
+        if full:
+            out["newton"] = nw[:m].cpu().numpy()
+        if K:
+            out["topk_pos"] = tp[:Q * K].cpu().numpy().reshape(Q, K)
+            out["topk_val"] = tv[:Q * K].cpu().numpy().reshape(Q, K)
+        return out
+
     def _host_num_params(self):
         """D of theta_t from the model's shape alone (no GPU context needed)."""
         k = int(self.embedding_size)

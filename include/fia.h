@@ -393,6 +393,67 @@ int fia_query_batch_newton(fia_ctx* ctx, int64_t num_queries, const int32_t* q_u
                            int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val,   /* device [Q*K] */
                            void* stream);
 
+/* Newton-corrected influence of HYPOTHETICAL ratings: fia_score_candidates with the candidate's own
+ * curvature in the system -- "what would this prediction do if the user rated b with y", one Newton
+ * step of the objective WITH the rating instead of a first-order estimate.  What-if ratings are asked
+ * for users with short histories, where one more rating is a large share of H (a mean over n_q
+ * ratings) and the first-order value is furthest off.
+ * Query q = (u, i), n = n_q; v, H, theta_t, M and C as in fia_group_influence.  Candidate
+ * c = (a, b, y) with e_c and g_c as in fia_score_candidates (user-side blocks zero unless a == u,
+ * item-side blocks zero unless b == i); both = (a == u and b == i):
+ *   H_c = (1/n) (2 g_c g_c^T + 2 e_c C * [both] + wd * diag(M))
+ *   b_c = (1/n) (2 e_c g_c + wd * M * theta_t)
+ *   newton_add[c] = v . (H + H_c)^-1 b_c
+ * The candidate counts once and the normalisation stays 1/n_q, as in fia_score_candidates and
+ * fia_group_influence.  Dropping H_c gives exactly fia_score_candidates' influence[c], and the sign
+ * convention is that call's: the Newton step's change of r-hat(u, i) after adding the rating is
+ * -newton_add[c].
+ * Closed form for every candidate that is not `both` (rank one plus a shift common to the query):
+ *   H" = H + (wd/n) * diag(M),  c = 2/n,  x" = H"^-1 v,  w" = H"^-1 (wd * M * theta_t) / n,
+ *   c" = x" . (wd * M * theta_t) / n
+ *   s = x" . g_c,  t = w" . g_c,  h = g_c^T H"^-1 g_c
+ *   newton_add = 2 e_c s / n + c" - c * s * (2 e_c h / n + t) / (1 + c * h)
+ * one factorisation per query and a quadratic form per candidate.  1 + c h is negative for some
+ * coupled queries (H indefinite through 2 e C): nothing assumes its sign; a zero denominator yields
+ * whatever the arithmetic yields.  A candidate sharing neither side has g_c = 0 and scores c"; a
+ * `both` candidate (g_c = v, and 2 e_c C is not rank one) gets one full solve of
+ * H" + (2/n) v v^T + (2 e_c / n) C, as own-pair rows do in fia_query_batch_newton -- they are
+ * expected to be few.
+ * There is no x argument: the call factorises for itself (fia_query_batch's x belongs to another
+ * system).  Arguments as fia_score_candidates: cand_offsets[0] == 0, non-decreasing,
+ * cand_offsets[Q] == total_cand; total_cand <= FIA_CAND_MAX_TOTAL and num_queries <=
+ * FIA_CAND_NEWTON_MAX_QUERIES (2^30: the partition's sort keys 2 q + side are 32-bit) are checked
+ * before anything is reserved or launched; K in [0, FIA_MAX_TOPK] with non-NULL top-K arrays;
+ * newton_add NULL with K == 0 is FIA_ERR_INVALID (no output requested); num_queries == 0 returns
+ * FIA_OK and launches nothing.  A candidate id outside [0, num_users) x [0, num_items) is never used
+ * as an index and scores NaN; a query with n_q = 0, or a query id out of range, gives NaN for all of
+ * its candidates.  topk: per query the K candidates of largest |newton_add| in fia_query_batch's
+ * order (ties: lower position first, NaN last) as position inside the query's candidate list
+ * (topk_pos) and signed value (topk_val), device arrays [Q*K]; unused slots hold -1 / NaN.  With
+ * newton_add NULL the values go to context scratch (total_cand doubles).
+ * A candidate's value depends on (query, a, b, y) alone: no floating-point atomics, and the bits are
+ * the same wherever the candidate sits in its list, wherever the query sits in the batch, whatever
+ * else is listed and however the batch is cut into launches.
+ * Needs params, index and a prepare (else FIA_ERR_STATE).  After fia_prepare_for the QUERIES must be
+ * covered; candidate entities may be any in-range id, and the results are bitwise those after
+ * fia_prepare.  Ordered on `stream`, no host synchronisation; it reads the entity Gram caches, so it
+ * joins a pending small-k Gram pass as fia_query_batch_newton does.
+ * Scratch: fia_query_batch_newton's record per query, bounded at 1 GiB per launch (a longer batch
+ * runs in chunks of queries; FIA_NEWTON_CHUNK lowers the chunk here too), and 16 bytes per candidate
+ * for the partition by (query, side).
+ * Sizes: MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32}.  The large-k models return
+ * FIA_ERR_UNSUPPORTED.  Phases (fia_set_profiling): 1 the per-query records, 4 the partition,
+ * 2 the scoring, 0 the `both` solves, 3 the top-K.  fia_version stays 100: no existing signature,
+ * struct or constant changed. */
+#define FIA_CAND_NEWTON_MAX_QUERIES (1LL << 30)
+int fia_score_candidates_newton(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item,
+                                const int64_t* cand_offsets,     /* device [Q+1], cand_offsets[0] == 0 */
+                                int64_t total_cand,              /* == cand_offsets[Q]                 */
+                                const int32_t* cand_user, const int32_t* cand_item, const float* cand_rating,
+                                double* newton_add,              /* device [total_cand], nullable      */
+                                int K, int64_t* topk_pos, double* topk_val,   /* device [Q*K]          */
+                                void* stream);
+
 /* Self-influence: the effect of a train rating on its OWN prediction (its leverage), for every
  * listed train row in one fused pass -- the scan that finds noisy or injected ratings, and what
  * turns a leave-one-out residual into a Cook's-distance style score.  The reference has no
