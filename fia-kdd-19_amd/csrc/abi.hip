@@ -715,6 +715,49 @@ int fia_score_candidates_newton(fia_ctx* c, int64_t Q, const int32_t* qu, const 
   })
 }
 
+int fia_edit_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* grp_offsets,
+                       int64_t num_groups, const int64_t* rem_offsets, int64_t total_rem, const int32_t* rem_row,
+                       const int64_t* add_offsets, int64_t total_add, const int32_t* add_user, const int32_t* add_item,
+                       const float* add_rating, double* edit, double* first_order, double* dtheta, int K,
+                       int64_t* topk_pos, double* topk_val, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    // the batch bounds come first: nothing of an oversized batch is looked at
+    if (Q < 0 || Q >= (1LL << 31)) return fail(c, FIA_ERR_INVALID, "num_queries out of range");
+    if (num_groups < 0 || num_groups > FIA_EDIT_MAX_GROUPS)
+      return fail(c, FIA_ERR_INVALID, "num_groups out of range [0, 2^31 - 1]: split the batch");
+    if (total_rem < 0 || total_rem > FIA_EDIT_MAX_MEMBERS)
+      return fail(c, FIA_ERR_INVALID, "total_rem out of range [0, 2^31 - 1]: split the batch");
+    if (total_add < 0 || total_add > FIA_EDIT_MAX_MEMBERS)
+      return fail(c, FIA_ERR_INVALID, "total_add out of range [0, 2^31 - 1]: split the batch");
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
+    if (K < 0 || K > FIA_MAX_TOPK) return fail(c, FIA_ERR_INVALID, "K must be in [0, FIA_MAX_TOPK]");
+    if (K > 0 && (!topk_pos || !topk_val)) return fail(c, FIA_ERR_INVALID, "null top-K output");
+    if (!edit && !first_order && !dtheta && K == 0)
+      return fail(c, FIA_ERR_INVALID, "no output requested (edit, first_order, dtheta, top-K)");
+    if (Q == 0 || (num_groups == 0 && K == 0)) return FIA_OK;
+    if (!qu || !qi || !grp_offsets) return fail(c, FIA_ERR_INVALID, "null query or offset array");
+    if (num_groups > 0 && (!rem_offsets || !add_offsets)) return fail(c, FIA_ERR_INVALID, "null member offset array");
+    if (total_rem > 0 && !rem_row) return fail(c, FIA_ERR_INVALID, "null removal array");
+    if (total_add > 0 && (!add_user || !add_item || !add_rating))
+      return fail(c, FIA_ERR_INVALID, "null addition array");
+    if (!fia::group_supported(c->p.model, c->p.k))
+      return fail(c, FIA_ERR_UNSUPPORTED,
+                  "fia_edit_influence is built for MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32}; the large-k "
+                  "models are not supported yet");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_edit_influence"); rc != FIA_OK) return rc;
+    // the Gram caches of a pending small-k pass are read: join it, as fia_group_influence does
+    if (hipError_t es = fia::join_prepare(c, s); es != hipSuccess) return hip_fail(c, es, "fia_edit_influence");
+    hipError_t e = fia::edit_influence(c, Q, qu, qi, grp_offsets, num_groups, rem_offsets, total_rem, rem_row,
+                                       add_offsets, total_add, add_user, add_item, add_rating, edit, first_order,
+                                       dtheta, K, topk_pos, topk_val, s);
+    if (e != hipSuccess) return hip_fail(c, e, "fia_edit_influence");
+    return FIA_OK;
+  })
+}
+
 int fia_set_profiling(fia_ctx* c, int phase_mask) {
   if (!c) return FIA_ERR_INVALID;
   c->profiling = (unsigned)phase_mask & ((1u << FIA_NUM_PHASES) - 1u);

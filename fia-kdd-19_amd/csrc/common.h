@@ -571,6 +571,16 @@ hipError_t score_candidates_newton(fia_ctx* c, int64_t Q, const int32_t* qu, con
                                    const int32_t* cand_item, const float* cand_rating, double* newton_add, int K,
                                    int64_t* topk_pos, double* topk_val, hipStream_t s);
 
+// fia_edit_influence (edit.hip): per edit set -- train rows removed, hypothetical ratings added --
+// the system downdated and updated and solved once; the sizes of group_supported; scratch:
+// c->rowrec, c->gxq (x_q for first_order, then the values of a top-K without `edit`), c->cand_pos,
+// c->cand_val
+hipError_t edit_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int64_t* grp_offsets,
+                          int64_t num_groups, const int64_t* rem_offsets, int64_t total_rem, const int32_t* rem_row,
+                          const int64_t* add_offsets, int64_t total_add, const int32_t* add_user,
+                          const int32_t* add_item, const float* add_rating, double* edit, double* first_order,
+                          double* dtheta, int K, int64_t* topk_pos, double* topk_val, hipStream_t s);
+
 // phase event helpers (no-ops unless profiling)
 void phase_begin(fia_ctx* c, int phase, hipStream_t s);
 void phase_end(fia_ctx* c, int phase, hipStream_t s);

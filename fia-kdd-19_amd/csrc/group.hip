@@ -211,6 +211,20 @@ hipError_t ensure_rowrec(fia_ctx* c, hipStream_t s) {
   return hipSuccess;
 }
 
+hipError_t launch_group_x(fia_ctx* c, const QueryArgs& A, int64_t Q, double* xq, hipStream_t s) {
+  GroupArgs Gr{};
+  Gr.Q = Q;
+  Gr.xq = xq;
+  hipError_t e = hipErrorInvalidValue;
+  dispatch_small(c->p.model, c->p.k, [&](auto m) {
+    using M = decltype(m);
+    const int64_t cap = solve_grid_cap(c, group_lds_bytes<M>());
+    hipLaunchKernelGGL(k_group_x<M>, dim3((unsigned)(Q < cap ? Q : cap)), dim3(kSolveThreads), 0, s, A, Gr);
+    e = hipGetLastError();
+  });
+  return e;
+}
+
 bool group_supported(int model, int k) {
   return dispatch_small(model, k, [](auto) {});
 }

@@ -1,6 +1,6 @@
 // Device code of the full-D per-query system, shared by small_solve.hip (k_solve, k_record_x and
-// the side-system solves' prologue), group.hip (fia_group_influence) and self.hip
-// (fia_self_influence): the LDS LDL^T, the
+// the side-system solves' prologue), group.hip (fia_group_influence), self.hip
+// (fia_self_influence) and edit.hip (fia_edit_influence): the LDS LDL^T, the
 // query prologue (theta_t, v = d r-hat / d theta_t, r-hat of one pair), the assembly of the
 // packed coupled Hessian from the two entity Gram caches and the removal of one train row from
 // it.  One wave (kSolveThreads) per system unless a function says otherwise.
@@ -247,6 +247,9 @@ __device__ __forceinline__ void stage_ncf(const QueryArgs& A, NCFWeights<M::ncf 
 // c->rowrec: train row -> {user, item, rating bits, user-major list position}, built once per
 // index (group.hip)
 hipError_t ensure_rowrec(fia_ctx* c, hipStream_t s);
+// group.hip's k_group_x for a caller in another unit (edit.hip): x_q = H^-1 v of the Q queries of
+// A with n_q > 0 into xq [Q * D], block order
+hipError_t launch_group_x(fia_ctx* c, const QueryArgs& A, int64_t Q, double* xq, hipStream_t s);
 // one-wave workgroups of `lds` bytes that the device keeps resident (160 KB of LDS per CU, at most
 // 16 per CU: 4 waves per SIMD at <= 128 VGPRs): the grid of a persistent full-D kernel
 inline int64_t solve_grid_cap(const fia_ctx* c, int64_t lds) {

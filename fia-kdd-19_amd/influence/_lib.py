@@ -45,6 +45,8 @@ SIGNATURES = {
     "fia_query_batch_newton": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
     "fia_score_candidates_newton": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P,
                                                    _P]),
+    "fia_edit_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P,
+                                          ctypes.c_int, _P, _P, _P]),
     "fia_num_params": (ctypes.c_int, [_P]),
     "fia_set_profiling": (ctypes.c_int, [_P, ctypes.c_int]),
     "fia_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I64)]),
@@ -427,6 +429,67 @@ class Context(object):
                                                   _ptr(cand_user), _ptr(cand_item), _ptr(cand_rating),
                                                   _ptr(newton_add), int(K), _ptr(topk_pos), _ptr(topk_val), _stream())
         self._check(rc, "fia_score_candidates_newton")
+
+    def edit_influence(self, qu, qi, grp_offsets, rem_offsets, rem_row, add_offsets, add_user, add_item,
+                       add_rating, edit=None, first_order=None, dtheta=None, K=0, topk_pos=None, topk_val=None):
+        """fia_edit_influence: for every edit set (group g of query q for g in
+        grp_offsets[q]:grp_offsets[q+1]; its removals rem_row[rem_offsets[g]:rem_offsets[g+1]],
+        train rows, and its additions add_offsets[g]:add_offsets[g+1] of add_user / add_item /
+        add_rating) the predicted change of r-hat once the rows are removed and the ratings added
+        together -- one system per group, solved again -- into edit (float64 [G]), its
+        first-order counterpart into first_order (float64 [G]) and the parameter step into dtheta
+        (float64 [G * D], reference theta order); with K the K groups of largest |edit| per query
+        (topk_pos int64 [Q * K] positions inside the query, topk_val float64 [Q * K]).  Offsets
+        are int64, rows and ids int32, ratings float32."""
+        import torch
+        for t, name in ((qu, "qu"), (qi, "qi"), (rem_row, "rem_row"), (add_user, "add_user"), (add_item, "add_item")):
+            self._need_int32(t, name)
+        if qi.numel() != qu.numel():
+            raise ValueError("qu and qi must have the same length")
+        Q = qu.numel()
+        if grp_offsets.dtype != torch.int64 or grp_offsets.numel() != Q + 1:
+            raise TypeError("grp_offsets must be a torch.int64 tensor of Q + 1 values")
+        for t, name in ((rem_offsets, "rem_offsets"), (add_offsets, "add_offsets")):
+            if t.dtype != torch.int64 or t.numel() < 1:
+                raise TypeError("%s must be a torch.int64 tensor of G + 1 values" % name)
+        G = rem_offsets.numel() - 1
+        if add_offsets.numel() != G + 1:
+            raise ValueError("rem_offsets and add_offsets must have the same length")
+        if add_rating is not None and add_rating.dtype != torch.float32:
+            raise TypeError("add_rating must be a torch.float32 tensor (got %s)" % add_rating.dtype)
+        for t, name in ((edit, "edit"), (first_order, "first_order"), (dtheta, "dtheta"), (topk_val, "topk_val")):
+            if t is not None and t.dtype != torch.float64:
+                raise TypeError("%s must be a torch.float64 tensor" % name)
+        if topk_pos is not None and topk_pos.dtype != torch.int64:
+            raise TypeError("topk_pos must be a torch.int64 tensor")
+        for t, name in ((qu, "qu"), (qi, "qi"), (grp_offsets, "grp_offsets"), (rem_offsets, "rem_offsets"),
+                        (rem_row, "rem_row"), (add_offsets, "add_offsets"), (add_user, "add_user"),
+                        (add_item, "add_item"), (add_rating, "add_rating"), (edit, "edit"),
+                        (first_order, "first_order"), (dtheta, "dtheta"), (topk_pos, "topk_pos"),
+                        (topk_val, "topk_val")):
+            if t is not None and not (t.is_cuda and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous device (cuda) tensor" % name)
+        K = int(K)
+        if edit is None and first_order is None and dtheta is None and K == 0:
+            raise ValueError("no output requested (edit, first_order, dtheta, top-K)")
+        for t, name in ((edit, "edit"), (first_order, "first_order")):
+            if t is not None and t.numel() < G:
+                raise ValueError("%s holds %d values, the batch has %d groups" % (name, t.numel(), G))
+        if dtheta is not None and dtheta.numel() < G * self.num_params():
+            raise ValueError("dtheta holds %d values, %d groups need %d" % (
+                dtheta.numel(), G, G * self.num_params()))
+        total_rem = rem_row.numel() if rem_row is not None else 0
+        total_add = add_user.numel() if add_user is not None else 0
+        if total_add and (add_item is None or add_rating is None
+                          or min(add_item.numel(), add_rating.numel()) < total_add):
+            raise ValueError("addition arrays hold fewer than total_add = %d values" % total_add)
+        if K and (topk_pos is None or topk_val is None or min(topk_pos.numel(), topk_val.numel()) < Q * K):
+            raise ValueError("top-K outputs must hold Q * K values")
+        rc = self.lib.fia_edit_influence(self.h, Q, _ptr(qu), _ptr(qi), _ptr(grp_offsets), G, _ptr(rem_offsets),
+                                         total_rem, _ptr(rem_row), _ptr(add_offsets), total_add, _ptr(add_user),
+                                         _ptr(add_item), _ptr(add_rating), _ptr(edit), _ptr(first_order),
+                                         _ptr(dtheta), K, _ptr(topk_pos), _ptr(topk_val), _stream())
+        self._check(rc, "fia_edit_influence")
 
     # ---- profiling ----
     def set_profiling(self, on, phases=None):

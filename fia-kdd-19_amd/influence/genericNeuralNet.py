@@ -646,6 +646,107 @@ class GenericNeuralNet(object):
             out["dtheta"] = dth[:G * D].cpu().numpy().reshape(G, D)
         return out
 
+    def _checked_edits(self, n_queries, edits):
+        """Host validation of get_edit_influence's edit sets (no GPU call): returns (grp_offsets
+        int64 [Q+1], rem_offsets int64 [G+1], rem_row int32, add_offsets int64 [G+1], add_user,
+        add_item int32, add_rating float32) or raises ValueError."""
+        if len(edits) != n_queries:
+            raise ValueError("edits must hold one sequence of groups per test index (%d, got %d)" % (
+                n_queries, len(edits)))
+        n_train = int(self.num_train_examples)
+        grp_off, rem_off, add_off, rows, adds = [0], [0], [0], [], []
+        for per_query in edits:
+            for grp in per_query:
+                if isinstance(grp, np.ndarray) or not hasattr(grp, "__len__") or len(grp) != 2:
+                    raise ValueError("a group must be a pair (remove_rows, add_triples)")
+                r = np.asarray(grp[0])
+                if r.size == 0:
+                    r = np.zeros(0, np.int64)
+                if r.ndim != 1:
+                    raise ValueError("remove_rows must be a 1-d array of train rows")
+                if r.dtype.kind not in "iu":
+                    raise ValueError("train rows must be integers (got dtype %s)" % r.dtype)
+                r = r.astype(np.int64)
+                if r.size and (r.min() < 0 or r.max() >= n_train):
+                    raise ValueError("train rows must lie in [0, %d)" % n_train)
+                if np.unique(r).size != r.size:
+                    raise ValueError("a group removes a train row more than once")
+                try:
+                    a = np.asarray(grp[1], np.float64)
+                except (TypeError, ValueError):
+                    raise ValueError("add_triples must be an array-like of (user, item, rating)")
+                if a.size == 0:
+                    a = np.zeros((0, 3))
+                if a.ndim != 2 or a.shape[1] != 3:
+                    raise ValueError("add_triples must have shape [m, 3]: (user, item, rating)")
+                if not np.isfinite(a).all():
+                    raise ValueError("added ids and ratings must be finite")
+                if (a[:, :2] != np.floor(a[:, :2])).any():
+                    raise ValueError("added ids must be integers")
+                if a.shape[0] and (a[:, 0].min() < 0 or a[:, 0].max() >= self.num_users or a[:, 1].min() < 0 or
+                                   a[:, 1].max() >= self.num_items):
+                    raise ValueError("added ids must lie in [0, %d) x [0, %d)" % (self.num_users, self.num_items))
+                rows.append(r)
+                adds.append(a)
+                rem_off.append(rem_off[-1] + r.size)
+                add_off.append(add_off[-1] + a.shape[0])
+            grp_off.append(len(rem_off) - 1)
+        rem_row = np.concatenate(rows) if rows else np.zeros(0, np.int64)
+        add = np.concatenate(adds) if adds else np.zeros((0, 3))
+        return (np.asarray(grp_off, np.int64), np.asarray(rem_off, np.int64), np.ascontiguousarray(rem_row, np.int32),
+                np.asarray(add_off, np.int64), np.ascontiguousarray(add[:, 0], np.int32),
+                np.ascontiguousarray(add[:, 1], np.int32), np.ascontiguousarray(add[:, 2], np.float32))
+
+    def get_edit_influence(self, test_indices, edits, K=0, first_order=True, dtheta=False):
+        """Joint effect of EDIT SETS -- training ratings removed and hypothetical ratings added
+        together -- on the predictions of test ratings (one fia_edit_influence call).  edits[q] is
+        a sequence of groups of test rating test_indices[q]; a group is a pair (remove_rows,
+        add_triples): an integer array of train rows and an array-like [m, 3] of (user, item,
+        rating), either may be empty.  For each group, with R the removals and A the additions,
+
+            edit        = v . (H - H_R + H_A)^-1 (b_R - b_A)     the edited system, solved again
+            first_order = (H^-1 v) . (b_R - b_A)
+
+        (include/fia.h): the predicted change of r-hat(u, i) once R is removed and A is added.
+        With no additions edit is get_group_influence's group; a single addition gives minus
+        get_candidate_newton_batch's value; replacing a rating is one removal and one addition on
+        the same pair.  A removed row sharing neither the test rating's user nor its item
+        contributes nothing; an addition counts once.  len(edits), the pairs, integer rows and ids,
+        their ranges, duplicate removals inside a group and K (an integer in [0, FIA_MAX_TOPK])
+        are checked on the host (ValueError) before any GPU call.  Returns dict(grp_offsets int64
+        [Q+1], edit float64 [G], first_order float64 [G] or None, dtheta float64 [G, D] in the
+        reference theta order or None, topk_pos int64 [Q, K] and topk_val float64 [Q, K] or None:
+        the K groups of largest |edit| per test rating as positions inside edits[q], -1 / NaN
+        where it has fewer than K groups) as numpy arrays.  The large-k models raise FIAError
+        (unsupported)."""
+        Q = len(test_indices)
+        go, ro, rr, ao, au, ai, ay = self._checked_edits(Q, edits)
+        if isinstance(K, bool) or int(K) != K or not 0 <= int(K) <= _lib.FIA_MAX_TOPK:
+            raise ValueError("K must be in [0, %d]" % _lib.FIA_MAX_TOPK)
+        K = int(K)
+        D = self._host_num_params()
+        import torch
+        G = ro.size - 1
+        qu, qi = self._query_tensors(test_indices)
+        dev = self.ctx.torch_device
+        # (the count rejects query ids out of range and queries outside a prepare_for cover)
+        self.ctx.count_related(qu, qi)
+        dv = lambda a, dt: torch.from_numpy(a).to(dev) if a.size else torch.empty(1, dtype=dt, device=dev)[:0]
+        f64 = lambda m: torch.empty(max(m, 1), dtype=torch.float64, device=dev)
+        ed = f64(G)
+        fo = f64(G) if first_order else None
+        dth = f64(G * D) if dtheta else None
+        tp = torch.empty(max(Q * K, 1), dtype=torch.int64, device=dev) if K else None
+        tv = f64(Q * K) if K else None
+        self.ctx.edit_influence(qu, qi, torch.from_numpy(go).to(dev), torch.from_numpy(ro).to(dev),
+                                dv(rr, torch.int32), torch.from_numpy(ao).to(dev), dv(au, torch.int32),
+                                dv(ai, torch.int32), dv(ay, torch.float32), ed, fo, dth, K, tp, tv)
+        return dict(grp_offsets=go, edit=ed[:G].cpu().numpy(),
+                    first_order=fo[:G].cpu().numpy() if first_order else None,
+                    dtheta=dth[:G * D].cpu().numpy().reshape(G, D) if dtheta else None,
+                    topk_pos=tp[:Q * K].cpu().numpy().reshape(Q, K) if K else None,
+                    topk_val=tv[:Q * K].cpu().numpy().reshape(Q, K) if K else None)
+
     def _checked_self_rows(self, train_indices, K, full):
         """Host validation of get_self_influence (no GPU call): returns (rows, K) with rows the
         int32 [n] train rows, or None for every train row, or raises ValueError."""

@@ -509,6 +509,79 @@ int fia_self_influence(fia_ctx* ctx,
                        int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val,   /* device [K] */
                        void* stream);
 
+/* Edit sets: the joint Newton effect on a prediction of train rows REMOVED and hypothetical ratings
+ * ADDED together -- "what if this user had rated X with 5 instead of 1" (one removal and one
+ * addition on the same pair), "what if a new user answers these five items", "what do these twenty
+ * injected ratings do together".  None of these is a sum of fia_group_influence and
+ * fia_score_candidates_newton outputs: every call solves a system of its own, and (H - H_R)^-1 b_R
+ * and (H + H_c)^-1 b_c do not combine.
+ * Query q = (u, i), n = n_q; v, H, theta_t, M, C and, for a train row j, m_j, e_j, g_j as in
+ * fia_group_influence; for an added triple c = (a, b, y), e_c and g_c as in
+ * fia_score_candidates_newton (user-side blocks zero unless a == u, item-side blocks zero unless
+ * b == i; both = (a == u and b == i)).  The groups of query q are g in [grp_offsets[q],
+ * grp_offsets[q+1]); group g has two member lists, the removals R = rem_row[rem_offsets[g] ..
+ * rem_offsets[g+1]) (train rows) and the additions A = entries [add_offsets[g] .. add_offsets[g+1])
+ * of add_user / add_item / add_rating:
+ *   H_R = (1/n) sum_{j in R} m_j (2 g_j g_j^T + 2 e_j C_j + wd * M)
+ *   b_R = (1/n) sum_{j in R} m_j (2 e_j g_j + wd * M * theta_t)
+ *   H_A = (1/n) sum_{c in A} (2 g_c g_c^T + 2 e_c C * [both] + wd * diag(M))
+ *   b_A = (1/n) sum_{c in A} (2 e_c g_c + wd * M * theta_t)
+ *   dtheta[g*D ..) = (H - H_R + H_A)^-1 (b_R - b_A)     exact fp64 LDL^T of the full coupled system
+ *   edit[g]        = v . dtheta       predicted change of r-hat(u, i) once R is removed and A is added
+ *   first_order[g] = (H^-1 v) . (b_R - b_A)
+ * An addition counts once and the normalisation stays 1/n_q, exactly as in
+ * fia_score_candidates_newton.  With A empty edit is fia_group_influence's group; with R empty and
+ * A = {c} it is -newton_add[c]; with H_R and H_A dropped it is first_order.
+ *   - Members are accumulated removals first, then additions, each in list order.  No floating-point
+ *     atomics: the bits depend on (query, the two lists) alone -- the same on every call, wherever
+ *     the group sits in its query and the query in the batch.
+ *   - A removed row with m_j = 0 changes no bit of the result (as in fia_group_influence).  An
+ *     addition sharing neither side has g_c = 0 and adds wd * diag(M) / n to the system and
+ *     wd * M * theta_t / n to b_A, as fia_score_candidates_newton scores c" for it.
+ *   - A group with no removal of m_j > 0 and no addition at all writes exactly +0.0 (edit,
+ *     first_order, every dtheta entry) without solving.
+ *   - A member listed twice is taken twice.
+ *   - A removal row outside [0, n_train), or an added id outside [0, num_users) x [0, num_items), is
+ *     never used as an index: that group is NaN, its neighbours are untouched.  n_q = 0, or a query
+ *     id out of range (never used as an index), gives NaN for all of the query's groups.
+ * edit, first_order and dtheta (reference theta order) may each be NULL.  topk (K in
+ * [0, FIA_MAX_TOPK]; 0 = off): per query the K groups of largest |edit| in fia_query_batch's order
+ * (|v| descending, ties: lower position first, NaN last) as the group's position inside its query
+ * (topk_pos) and signed value (topk_val), device arrays [Q*K]; unused slots hold -1 / NaN.  With edit
+ * NULL the values go to context scratch (num_groups doubles).  All three outputs NULL with K == 0 is
+ * FIA_ERR_INVALID.
+ * grp_offsets[0] == 0, non-decreasing, grp_offsets[Q] == num_groups; rem_offsets and add_offsets
+ * [G+1] likewise with total_rem and total_add.  num_groups <= FIA_EDIT_MAX_GROUPS, total_rem and
+ * total_add <= FIA_EDIT_MAX_MEMBERS (2^31 - 1 each): a larger batch is refused with FIA_ERR_INVALID
+ * before anything is reserved or launched -- split it.  num_queries == 0, or num_groups == 0 with
+ * K == 0, returns FIA_OK and launches nothing.
+ * Needs params, index and a prepare (else FIA_ERR_STATE).  After fia_prepare_for only the QUERIES
+ * must be covered: members are read from the parameter tables and the dense NCF layer-1 rows, which
+ * every prepare writes for all entities, and the results are bitwise those after fia_prepare.
+ * Ordered on `stream`, no host synchronisation; it reads the entity Gram caches, so it joins a
+ * pending small-k Gram pass as fia_group_influence does.
+ * Sizes: MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32} (the full packed system of a group in
+ * LDS).  The large-k models (MF k in {128, 256}, NCF k in {64, 128, 256}) return
+ * FIA_ERR_UNSUPPORTED: they are the follow-up, as fia_group_influence's device-memory systems were
+ * to its first version.  Phases (fia_set_profiling): 1 the solves, 3 the top-K.  fia_version stays
+ * 100: no existing signature, struct or constant changed. */
+#define FIA_EDIT_MAX_GROUPS ((1LL << 31) - 1)
+#define FIA_EDIT_MAX_MEMBERS ((1LL << 31) - 1)
+int fia_edit_influence(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item,
+                       const int64_t* grp_offsets,  /* device [Q+1]: groups of query q                */
+                       int64_t num_groups,          /* == grp_offsets[Q]                              */
+                       const int64_t* rem_offsets,  /* device [G+1]: removals of group g              */
+                       int64_t total_rem,           /* == rem_offsets[G]                              */
+                       const int32_t* rem_row,      /* device [total_rem]: train rows                 */
+                       const int64_t* add_offsets,  /* device [G+1]: additions of group g             */
+                       int64_t total_add,           /* == add_offsets[G]                              */
+                       const int32_t* add_user, const int32_t* add_item, const float* add_rating,
+                       double* edit,                /* device [G], nullable                           */
+                       double* first_order,         /* device [G], nullable                           */
+                       double* dtheta,              /* device [G*D], reference theta order, nullable  */
+                       int K, int64_t* topk_pos, double* topk_val,   /* device [Q*K]                  */
+                       void* stream);
+
 /* Number of restricted parameters D of the registered model (0 if none). */
 int fia_num_params(const fia_ctx* ctx);
 
