@@ -758,6 +758,79 @@ int fia_edit_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* 
   })
 }
 
+int fia_count_related_pair(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int32_t* qj,
+                           int64_t* offsets, int64_t* total_out, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    if (!c->idx.valid) return fail(c, FIA_ERR_STATE, "fia_build_index has not been called");
+    if (Q < 0 || Q >= (1LL << 31)) return fail(c, FIA_ERR_INVALID, "num_queries out of range");
+    if (!offsets || (Q > 0 && (!qu || !qi || !qj))) return fail(c, FIA_ERR_INVALID, "null query array");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_count_related_pair"); rc != FIA_OK) return rc;
+    hipError_t e = hipSuccess;
+    if (total_out) {
+      e = c->flag.reserve(64, s);
+      if (e != hipSuccess) return hip_fail(c, e, "fia_count_related_pair");
+      e = hipMemsetAsync(c->flag.ptr, 0, 64, s);
+      if (e != hipSuccess) return hip_fail(c, e, "fia_count_related_pair");
+    }
+    e = fia::count_related_pair(c, Q, qu, qi, qj, offsets, s);
+    // the cover of both pairs: (u, i) and (u, j)
+    for (const int32_t* it : {qi, qj}) {
+      if (e == hipSuccess && total_out) e = fia::check_cover(c, Q, qu, it, c->flag.as<int32_t>() + 2, s);
+      if (e == hipSuccess && total_out) e = fia::check_cover_small(c, Q, qu, it, c->flag.as<int32_t>() + 2, s);
+    }
+    if (e != hipSuccess) return hip_fail(c, e, "fia_count_related_pair");
+    if (total_out) {
+      int32_t flags[4] = {0, 0, 0, 0};
+      e = hipMemcpyAsync(total_out, offsets + Q, sizeof(int64_t), hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(flags, c->flag.ptr, sizeof(flags), hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      if (e != hipSuccess) return hip_fail(c, e, "fia_count_related_pair");
+      if (flags[1]) return fail(c, FIA_ERR_INVALID, "query ids out of range [0, num_users) x [0, num_items)");
+      if (flags[2])
+        return fail(c, FIA_ERR_STATE, "a query's user or one of its two items has no Hessian cache: it was not among "
+                                      "the queries of the last fia_prepare_for");
+    }
+    return FIA_OK;
+  })
+}
+
+int fia_pair_batch(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int32_t* qj,
+                   const int64_t* offsets, int64_t total_rel, int32_t* rel_idx, double* influence, double* x_out,
+                   double* diff, int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    // the batch bounds come first: nothing of an oversized batch is looked at
+    if (Q < 0 || Q > FIA_PAIR_MAX_QUERIES)
+      return fail(c, FIA_ERR_INVALID, "num_queries out of range [0, 2^30]: split the batch");
+    // a rating's position inside its query's related list is kept in 32 bits by the top-K selection
+    if (total_rel < 0 || total_rel > FIA_PAIR_MAX_TOTAL_REL)
+      return fail(c, FIA_ERR_INVALID, "total_rel out of range [0, 2^31 - 1]: split the batch");
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
+    if (K < 0 || K > FIA_MAX_TOPK) return fail(c, FIA_ERR_INVALID, "K must be in [0, FIA_MAX_TOPK]");
+    if (K > 0 && (!topk_pos || !topk_idx || !topk_val)) return fail(c, FIA_ERR_INVALID, "null top-K output");
+    if (!rel_idx && !influence && !x_out && !diff && K == 0)
+      return fail(c, FIA_ERR_INVALID, "no output requested (rel_idx, influence, x_out, diff, top-K)");
+    if (Q == 0) return FIA_OK;
+    if (!qu || !qi || !qj || !offsets) return fail(c, FIA_ERR_INVALID, "null query or offset array");
+    if (!fia::pair_supported(c->p.model, c->p.k))
+      return fail(c, FIA_ERR_UNSUPPORTED,
+                  "fia_pair_batch is built for MF k in {8, 16, 32} and NCF k in {8, 16} (the three-block system in "
+                  "one workgroup's LDS); MF k = 64, NCF k = 32 and the large-k models are not supported yet");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_pair_batch"); rc != FIA_OK) return rc;
+    // the Gram caches of a pending small-k pass are read: join it, as fia_group_influence does
+    if (hipError_t es = fia::join_prepare(c, s); es != hipSuccess) return hip_fail(c, es, "fia_pair_batch");
+    hipError_t e = fia::pair_batch(c, Q, qu, qi, qj, offsets, total_rel, rel_idx, influence, x_out, diff, K, topk_pos,
+                                   topk_idx, topk_val, s);
+    if (e != hipSuccess) return hip_fail(c, e, "fia_pair_batch");
+    return FIA_OK;
+  })
+}
+
 int fia_set_profiling(fia_ctx* c, int phase_mask) {
   if (!c) return FIA_ERR_INVALID;
   c->profiling = (unsigned)phase_mask & ((1u << FIA_NUM_PHASES) - 1u);

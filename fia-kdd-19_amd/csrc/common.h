@@ -581,6 +581,18 @@ hipError_t edit_influence(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_
                           const int32_t* add_item, const float* add_rating, double* edit, double* first_order,
                           double* dtheta, int K, int64_t* topk_pos, double* topk_val, hipStream_t s);
 
+// fia_count_related_pair / fia_pair_batch (pair.hip): the system of the gap r-hat(u, i) - r-hat(u, j)
+// over theta_t = (theta_u, theta_i, theta_j) and the list R_u ++ C_i ++ C_j, assembled in LDS from
+// the three Gram caches and solved once per query; the sizes of pair_supported; scratch: c->qscan
+// and c->flag (the count), c->rec (two half records per query), c->coff (the tiles' first
+// queries), c->cand_pos, c->cand_val
+bool pair_supported(int model, int k);
+hipError_t count_related_pair(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int32_t* qj,
+                              int64_t* offsets, hipStream_t s);
+hipError_t pair_batch(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int32_t* qj,
+                      const int64_t* offsets, int64_t total_rel, int32_t* rel_idx, double* influence, double* x_out,
+                      double* diff, int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val, hipStream_t s);
+
 // phase event helpers (no-ops unless profiling)
 void phase_begin(fia_ctx* c, int phase, hipStream_t s);
 void phase_end(fia_ctx* c, int phase, hipStream_t s);

@@ -47,6 +47,8 @@ SIGNATURES = {
                                                    _P]),
     "fia_edit_influence": (ctypes.c_int, [_P, _I64, _P, _P, _P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P,
                                           ctypes.c_int, _P, _P, _P]),
+    "fia_count_related_pair": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    "fia_pair_batch": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
     "fia_num_params": (ctypes.c_int, [_P]),
     "fia_set_profiling": (ctypes.c_int, [_P, ctypes.c_int]),
     "fia_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I64)]),
@@ -490,6 +492,70 @@ class Context(object):
                                          _ptr(add_item), _ptr(add_rating), _ptr(edit), _ptr(first_order),
                                          _ptr(dtheta), K, _ptr(topk_pos), _ptr(topk_val), _stream())
         self._check(rc, "fia_edit_influence")
+
+    def count_related_pair(self, qu, qi, qj, offsets=None, want_total=True):
+        """fia_count_related_pair: offsets (int64 [Q + 1]) of the pair queries' related lists
+        R_u ++ C_i ++ C_j and, with want_total, their total on the host (then out-of-range ids and
+        entities outside a prepare_for cover raise)."""
+        import torch
+        for t, name in ((qu, "qu"), (qi, "qi"), (qj, "qj")):
+            self._need_int32(t, name)
+        Q = qu.numel()
+        if qi.numel() != Q or qj.numel() != Q:
+            raise ValueError("qu, qi and qj must have the same length")
+        if offsets is None:
+            offsets = torch.empty(Q + 1, dtype=torch.int64, device=self.torch_device)
+        total = ctypes.c_int64(0)
+        rc = self.lib.fia_count_related_pair(self.h, Q, _ptr(qu), _ptr(qi), _ptr(qj), _ptr(offsets),
+                                             ctypes.byref(total) if want_total else None, _stream())
+        self._check(rc, "fia_count_related_pair")
+        return offsets, (total.value if want_total else None)
+
+    def pair_batch(self, qu, qi, qj, offsets, total, rel_idx=None, influence=None, x=None, diff=None, K=0,
+                   topk_pos=None, topk_idx=None, topk_val=None):
+        """fia_pair_batch: for every pair query (qu, qi, qj) the influence of every rating of
+        R_u ++ C_i ++ C_j on the gap r-hat(u, i) - r-hat(u, j) -- one system over (theta_u, theta_i,
+        theta_j), solved once -- into influence (float64 [total]), the train rows into rel_idx
+        (int32 [total]), x = H^-1 v into x (float64 [Q * 3 * D / 2], the extended reference theta
+        order), the gap into diff (float64 [Q]) and, with K, the K ratings of largest |influence|
+        per query (topk_pos / topk_idx int64 [Q * K], topk_val float64 [Q * K]).  offsets / total as
+        count_related_pair returns them."""
+        import torch
+        for t, name in ((qu, "qu"), (qi, "qi"), (qj, "qj"), (rel_idx, "rel_idx")):
+            self._need_int32(t, name)
+        Q = qu.numel()
+        if qi.numel() != Q or qj.numel() != Q:
+            raise ValueError("qu, qi and qj must have the same length")
+        if offsets.dtype != torch.int64 or offsets.numel() != Q + 1:
+            raise TypeError("offsets must be a torch.int64 tensor of Q + 1 values")
+        for t, name in ((influence, "influence"), (x, "x"), (diff, "diff"), (topk_val, "topk_val")):
+            if t is not None and t.dtype != torch.float64:
+                raise TypeError("%s must be a torch.float64 tensor" % name)
+        for t, name in ((topk_pos, "topk_pos"), (topk_idx, "topk_idx")):
+            if t is not None and t.dtype != torch.int64:
+                raise TypeError("%s must be a torch.int64 tensor" % name)
+        for t, name in ((qu, "qu"), (qi, "qi"), (qj, "qj"), (offsets, "offsets"), (rel_idx, "rel_idx"),
+                        (influence, "influence"), (x, "x"), (diff, "diff"), (topk_pos, "topk_pos"),
+                        (topk_idx, "topk_idx"), (topk_val, "topk_val")):
+            if t is not None and not (t.is_cuda and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous device (cuda) tensor" % name)
+        # (an oversized total is the library's to refuse, before it looks at any array)
+        if 0 <= total < 2 ** 31:
+            for t, name in ((rel_idx, "rel_idx"), (influence, "influence")):
+                if t is not None and t.numel() < total:
+                    raise ValueError("%s holds %d values, the batch has %d related ratings" % (name, t.numel(), total))
+        if x is not None and x.numel() < Q * (3 * self.num_params() // 2):
+            raise ValueError("x holds %d values, %d queries need %d" % (x.numel(), Q, Q * (3 * self.num_params() // 2)))
+        if diff is not None and diff.numel() < Q:
+            raise ValueError("diff holds %d values, the batch has %d queries" % (diff.numel(), Q))
+        K = int(K)
+        if K > 0 and (topk_pos is None or topk_idx is None or topk_val is None
+                      or min(topk_pos.numel(), topk_idx.numel(), topk_val.numel()) < Q * K):
+            raise ValueError("top-K outputs must hold Q * K values")
+        rc = self.lib.fia_pair_batch(self.h, Q, _ptr(qu), _ptr(qi), _ptr(qj), _ptr(offsets), int(total),
+                                     _ptr(rel_idx), _ptr(influence), _ptr(x), _ptr(diff), K, _ptr(topk_pos),
+                                     _ptr(topk_idx), _ptr(topk_val), _stream())
+        self._check(rc, "fia_pair_batch")
 
     # ---- profiling ----
     def set_profiling(self, on, phases=None):

@@ -103,11 +103,17 @@ class GenericNeuralNet(object):
         self._upload_params()
         self.ctx.prepare()
 
-    def prepare_for(self, test_indices):
+    def prepare_for(self, test_indices, other_items=None):
         """Rebuild the Hessian caches for only the users/items of these test ratings
         (fia_prepare_for: one GPU's share of a sharded query set at large k).  Queries
-        outside the set then raise FIAError until the next prepare."""
+        outside the set then raise FIAError until the next prepare.  other_items (optional,
+        one item per test rating): also cover the pairs (u_t, other_items[t]), the j's of a
+        shard's get_pair_influence_batch calls."""
+        oj = None if other_items is None else self._checked_other_items(test_indices, other_items)
         qu, qi = self._query_tensors(test_indices)
+        if oj is not None:
+            import torch
+            qu, qi = torch.cat([qu, qu]), torch.cat([qi, torch.from_numpy(oj).to(self.ctx.torch_device)])
         self.ctx.prepare_for(qu, qi)
 
     def get_all_params(self):
@@ -855,6 +861,73 @@ class GenericNeuralNet(object):
         if full:
             out["rel_idx"] = rel[:total].cpu().numpy().astype(np.int64)
             out["newton"] = nw[:total].cpu().numpy()
+        if K:
+            out["topk_pos"] = tp[:Q * K].cpu().numpy().reshape(Q, K)
+            out["topk_idx"] = ti[:Q * K].cpu().numpy().reshape(Q, K)
+            out["topk_val"] = tv[:Q * K].cpu().numpy().reshape(Q, K)
+        return out
+
+    def _checked_other_items(self, test_indices, other_items, distinct=False):
+        """Host validation of the second items of pair queries (no GPU call): int32 [Q], one
+        in-range item per test rating -- with `distinct`, never the test rating's own item -- or
+        ValueError."""
+        j = np.asarray(other_items)
+        if j.size == 0:
+            j = np.zeros(0, np.int64)
+        if j.ndim != 1 or j.size != len(test_indices):
+            raise ValueError("other_items must hold one item per test index (%d)" % len(test_indices))
+        if j.dtype.kind not in "iu":
+            raise ValueError("other_items must be integers (got dtype %s)" % j.dtype)
+        j = j.astype(np.int64)
+        if j.size and (j.min() < 0 or j.max() >= self.num_items):
+            raise ValueError("other_items must lie in [0, %d)" % self.num_items)
+        if distinct:
+            for t, b in zip(test_indices, j):
+                if self._test_pair(t)[1] == b:
+                    raise ValueError("other_items[t] must differ from the test rating's own item (test row %s)" % t)
+        return np.ascontiguousarray(j, np.int32)
+
+    def get_pair_influence_batch(self, test_indices, other_items, K=1, full=True, return_x=True):
+        """Which ratings put item i above item j for a user (one fia_pair_batch call): query t is
+        the test rating (u_t, i_t) against j = other_items[t], and the explained number is the gap
+        d = r-hat(u, i) - r-hat(u, j).  Its system is its own -- theta_t = (theta_u, theta_i,
+        theta_j), the related list R_u ++ C_i ++ C_j, one Hessian, one solve (include/fia.h) -- not
+        the difference of two get_influence_batch results.  influence[offsets[t] + p] is the
+        predicted change of d when the p-th rating of that list is removed.  The length of
+        other_items, integer in-range items, j != i_t and K (an integer in [0, FIA_MAX_TOPK]) are
+        checked on the host (ValueError) before any GPU call.  Returns dict(offsets int64 [Q + 1],
+        diff float64 [Q]; with full rel_idx int64 and influence float64 [total]; with return_x x
+        float64 [Q, 3 D / 2] in the extended reference theta order (MF [p_u, q_i, q_j, b_u, b_i,
+        b_j], NCF [Pm_u, Qm_i, Qm_j, Pg_u, Qg_i, Qg_j]); with K topk_pos, topk_idx int64 [Q, K] and
+        topk_val float64 [Q, K] by |influence|, ties to the lower position, -1 / -1 / NaN in unused
+        slots) as numpy arrays.  MF k = 64, NCF k = 32 and the large-k models raise FIAError
+        (unsupported)."""
+        if isinstance(K, bool) or int(K) != K or not 0 <= int(K) <= _lib.FIA_MAX_TOPK:
+            raise ValueError("K must be in [0, %d]" % _lib.FIA_MAX_TOPK)
+        K = int(K)
+        oj = self._checked_other_items(test_indices, other_items, distinct=True)
+        import torch
+        qu, qi = self._query_tensors(test_indices)
+        Q = qu.numel()
+        dev = self.ctx.torch_device
+        qj = torch.from_numpy(oj).to(dev) if Q else torch.empty(1, dtype=torch.int32, device=dev)[:0]
+        # (the count rejects query ids out of range and entities outside a prepare_for cover)
+        offsets, total = self.ctx.count_related_pair(qu, qi, qj)
+        D3 = 3 * self._host_num_params() // 2
+        f64 = lambda m: torch.empty(max(m, 1), dtype=torch.float64, device=dev)
+        i64 = lambda m: torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+        rel = torch.empty(max(total, 1), dtype=torch.int32, device=dev) if full else None
+        infl = f64(total) if full else None
+        x = f64(Q * D3) if return_x else None
+        diff = f64(Q)
+        tp, ti, tv = (i64(Q * K), i64(Q * K), f64(Q * K)) if K else (None, None, None)
+        self.ctx.pair_batch(qu, qi, qj, offsets, total, rel, infl, x, diff, K, tp, ti, tv)
+        out = dict(offsets=offsets.cpu().numpy(), diff=diff[:Q].cpu().numpy())
+        if full:
+            out["rel_idx"] = rel[:total].cpu().numpy().astype(np.int64)
+            out["influence"] = infl[:total].cpu().numpy()
+        if return_x:
+            out["x"] = x[:Q * D3].cpu().numpy().reshape(Q, D3)
         if K:
             out["topk_pos"] = tp[:Q * K].cpu().numpy().reshape(Q, K)
             out["topk_idx"] = ti[:Q * K].cpu().numpy().reshape(Q, K)

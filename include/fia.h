@@ -31,6 +31,9 @@
  *   (none: one test point per call, mf:179 -- every      fia_self_influence
  *     train row's effect on its OWN prediction, the
  *     leverage scan for suspicious ratings)
+ *   (none: one test point per call, mf:179 -- which     fia_count_related_pair + fia_pair_batch
+ *     ratings put item i above item j for a user, the
+ *     influence on r-hat(u, i) - r-hat(u, j))
  *
  * Conventions
  *   - All array arguments are DEVICE pointers owned by the caller (PyTorch).
@@ -581,6 +584,84 @@ int fia_edit_influence(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user,
                        double* dtheta,              /* device [G*D], reference theta order, nullable  */
                        int K, int64_t* topk_pos, double* topk_val,   /* device [Q*K]                  */
                        void* stream);
+
+/* Pair queries: which ratings put item i ABOVE item j for a user.  A recommender shows an order, and
+ * what decides it is the gap d = r-hat(u, i) - r-hat(u, j).  Subtracting two fia_query_batch results
+ * is not FIA's answer for d: the two calls restrict to different parameter sets, use different
+ * related lists and normalisations, and each re-solves the shared user block against one item only.
+ * The reference has no counterpart (one test point per call, matrix_factorization.py:179).
+ * Pair query q = (u, i, j) = (q_user[q], q_item_i[q], q_item_j[q]), i != j.  Side block size
+ * Ds = k + 1 (MF) or 2k (NCF), D3 = 3 * Ds.
+ *   theta_t = (theta_u, theta_i, theta_j): MF (p_u, b_u), (q_i, b_i), (q_j, b_j); NCF (Pm_u, Pg_u),
+ *             (Qm_i, Qg_i), (Qm_j, Qg_j)
+ *   rel     = where(user == u) ++ where(item == i) ++ where(item == j), each in ascending train-row
+ *             order; n = |R_u| + |C_i| + |C_j|.  A train row (u, i) or (u, j) sits in rel twice; no
+ *             row sits three times.
+ *   For position p with train row (a, b, y): e_p = r-hat(a, b) - y and g_p = d r-hat(a, b) / d theta_t,
+ *             whose user block is zero unless a == u, whose i block unless b == i and whose j block
+ *             unless b == j -- whichever list the position is in, as fia_query_batch treats the own pair.
+ *   H       = (2/n) sum_p (g_p g_p^T + e_p d2 r-hat_p) + wd * diag(M) + damping * I, M as in
+ *             fia_group_influence; d2 r-hat is nonzero only for own-pair rows: MF I on the (p_u, q_i)
+ *             cross block for (u, i) and on the (p_u, q_j) cross block for (u, j), NCF diag(W3g) on the
+ *             (Pg_u, Qg_i) and (Pg_u, Qg_j) cross blocks.  From the caches, with v^i = d r-hat(u, i) /
+ *             d (theta_u, theta_i), v^j likewise, A_u / B_i / B_j the entity Grams and (cd, es) = (rows of
+ *             the pair in train, the sum of their residuals):
+ *               H_uu = (2/n) (A_u + cd_i v^i_u v^i_u^T + cd_j v^j_u v^j_u^T)
+ *               H_ii = (2/n) (B_i + cd_i v^i_i v^i_i^T)            H_jj likewise
+ *               H_iu = (2/n) 2 (cd_i v^i_i v^i_u^T + es_i C)       H_ju likewise       H_ij = 0
+ *             plus the diagonal terms: block diagonal when neither pair is a train row.
+ *   v       = d d / d theta_t = (v^i_u - v^j_u, v^i_i, -v^j_j)
+ *   x       = H^-1 v: exact fp64 LDL^T, nothing assumed about a pivot's sign (coupling makes H indefinite)
+ *   influence[offsets[q] + p] = x . (2 e_p g_p + wd * M * theta_t) / n     fia_query_batch's expression
+ *   diff[q] = r-hat(u, i) - r-hat(u, j)                                    current parameters, fp64
+ *   x_out [Q * D3]: the reference theta order, extended: MF [p_u, q_i, q_j, b_u, b_i, b_j],
+ *             NCF [Pm_u, Qm_i, Qm_j, Pg_u, Qg_i, Qg_j]
+ * topk (K in [0, FIA_MAX_TOPK]; 0 = off): per query, as fia_query_batch -- |value| descending, lower
+ * related position first, NaN last -- as position in the pair's own related list (topk_pos), train row
+ * (topk_idx) and signed value (topk_val), device arrays [Q*K]; unused slots hold -1 / -1 / NaN.
+ *   - n = 0 writes no ratings, a NaN x and a NaN-free diff.
+ *   - An id outside [0, num_users) x [0, num_items) is never used as an index and counts as n = 0; its
+ *     diff is NaN.
+ *   - i == j also counts as n = 0 (the two item blocks would be one parameter twice); its diff is +0.0.
+ *   - No floating-point atomics: a query's bits do not depend on where it sits in the batch or on what
+ *     else is in it.  (A query with a train-row pair takes one full-range LDL^T, one with none three
+ *     block-range ones: the two routes are not claimed to agree bitwise, and a query never changes route.)
+ * fia_count_related_pair: fia_count_related's contract for the pair list (offsets device int64 [Q+1];
+ * with total_out the total is copied to the host, the stream synchronised, out-of-range ids reported as
+ * FIA_ERR_INVALID, and a query whose u, i or j is outside a fia_prepare_for cover as FIA_ERR_STATE).
+ * Without total_out, bad ids and i == j count zero.  Needs the index only.
+ * fia_pair_batch: rel_idx (int32 train rows), influence, x_out and diff are each nullable; all four NULL
+ * with K == 0 is FIA_ERR_INVALID.  total_rel must equal offsets[Q].  With influence NULL and K > 0
+ * nothing of length total_rel is written.  num_queries == 0 returns FIA_OK and launches nothing.
+ * Batch limit: total_rel <= FIA_PAIR_MAX_TOTAL_REL (2^31 - 1: the top-K keeps a 32-bit position) and
+ * num_queries <= FIA_PAIR_MAX_QUERIES (2^30: two half records per query, indexed in 32 bits); a larger
+ * batch is refused with FIA_ERR_INVALID before anything is reserved or launched -- split it.  Checks
+ * run in fia_edit_influence's order: bounds, state, outputs, the empty batch, nulls, support.
+ * Needs params, index and a prepare (else FIA_ERR_STATE).  After fia_prepare_for the cover must hold
+ * u, i AND j of every query (fia_prepare_for with the pairs (u, i) and (u, j)); the results are then
+ * bitwise those after fia_prepare.  Ordered on `stream`, no host synchronisation; it reads the entity
+ * Gram caches, so it joins a pending small-k Gram pass as fia_group_influence does.  Stores are per
+ * element: the outputs need only their types' natural alignment.
+ * Sizes: MF k in {8, 16, 32} and NCF k in {8, 16} -- those whose packed D3 triangle (MF k=32: 4,950
+ * doubles), vectors and staged NCF W1 fit one workgroup's LDS; MF k=64 would need 153 KB for the
+ * triangle alone.  Every other size (MF k=64, NCF k=32, the large-k models) is FIA_ERR_UNSUPPORTED.
+ * Phases (fia_set_profiling): 4 the count and scan (fia_count_related_pair) and the related rows,
+ * 1 the solves, 2 the scoring, 3 the top-K.  fia_version stays 100: no existing signature, struct or
+ * constant changed. */
+#define FIA_PAIR_MAX_TOTAL_REL ((1LL << 31) - 1)
+#define FIA_PAIR_MAX_QUERIES (1LL << 30)
+int fia_count_related_pair(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item_i,
+                           const int32_t* q_item_j, int64_t* offsets, int64_t* total_out, void* stream);
+int fia_pair_batch(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item_i,
+                   const int32_t* q_item_j,
+                   const int64_t* offsets,         /* device [Q+1], from fia_count_related_pair */
+                   int64_t total_rel,              /* == offsets[Q]                              */
+                   int32_t* rel_idx,               /* device [total_rel], nullable               */
+                   double* influence,              /* device [total_rel], nullable               */
+                   double* x_out,                  /* device [Q*D3], nullable                    */
+                   double* diff,                   /* device [Q], nullable                       */
+                   int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val,   /* device [Q*K] */
+                   void* stream);
 
 /* Number of restricted parameters D of the registered model (0 if none). */
 int fia_num_params(const fia_ctx* ctx);
