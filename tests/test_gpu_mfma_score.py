@@ -290,7 +290,7 @@ class RawModel(object):
     """A fia context set up through influence._lib alone (the facade's constructor always
     runs a full fia_prepare; here the first prepare is the caller's)."""
 
-    def __init__(self, model, k, U, I, train, params, prepare=True):
+    def __init__(self, model, k, U, I, train, params, prepare=True, wd=WD, damping=DAMPING):
         import torch
         from influence import _lib
         self.torch, self.lib = torch, _lib
@@ -298,7 +298,7 @@ class RawModel(object):
         self.ctx = _lib.Context(0)
         self.tables = [torch.from_numpy(np.ascontiguousarray(params[n], np.float32)).to(self.dev) for n in params]
         self.ctx.set_params(_lib.FIA_MODEL_MF if model == "MF" else _lib.FIA_MODEL_NCF, k, U, I, self.tables,
-                            WD, DAMPING)
+                            wd, damping)
         tu, ti, tr = train
         self.train = [torch.from_numpy(np.ascontiguousarray(a, t)).to(self.dev)
                       for a, t in ((tu, np.int32), (ti, np.int32), (tr, np.float32))]
