@@ -831,6 +831,86 @@ int fia_pair_batch(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, 
   })
 }
 
+int fia_count_related_slate(fia_ctx* c, int64_t Q, const int32_t* qu, const int64_t* slate_offsets,
+                            int64_t total_items, const int32_t* slate_item, int64_t* offsets, int64_t* total_out,
+                            void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    if (!c->idx.valid) return fail(c, FIA_ERR_STATE, "fia_build_index has not been called");
+    if (Q < 0 || Q > FIA_SLATE_MAX_TOTAL_ITEMS) return fail(c, FIA_ERR_INVALID, "num_queries out of range");
+    if (total_items < 0 || total_items > FIA_SLATE_MAX_TOTAL_ITEMS)
+      return fail(c, FIA_ERR_INVALID, "total_items out of range [0, 2^30]: split the batch");
+    if (!offsets || (Q > 0 && (!qu || !slate_offsets)) || (total_items > 0 && !slate_item))
+      return fail(c, FIA_ERR_INVALID, "null query array");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_count_related_slate"); rc != FIA_OK) return rc;
+    hipError_t e = hipSuccess;
+    if (total_out) {
+      e = c->flag.reserve(64, s);
+      if (e != hipSuccess) return hip_fail(c, e, "fia_count_related_slate");
+      e = hipMemsetAsync(c->flag.ptr, 0, 64, s);
+      if (e != hipSuccess) return hip_fail(c, e, "fia_count_related_slate");
+    }
+    // (the scan checks the cover of u and of every slate item itself)
+    e = fia::count_related_slate(c, Q, qu, slate_offsets, total_items, slate_item, offsets, total_out != nullptr, s);
+    if (e != hipSuccess) return hip_fail(c, e, "fia_count_related_slate");
+    if (total_out) {
+      int32_t flags[4] = {0, 0, 0, 0};
+      e = hipMemcpyAsync(total_out, offsets + Q, sizeof(int64_t), hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipMemcpyAsync(flags, c->flag.ptr, sizeof(flags), hipMemcpyDeviceToHost, s);
+      if (e == hipSuccess) e = hipStreamSynchronize(s);
+      if (e != hipSuccess) return hip_fail(c, e, "fia_count_related_slate");
+      if (flags[1])
+        return fail(c, FIA_ERR_INVALID, "a slate's ids are out of range [0, num_users) x [0, num_items), it repeats an "
+                                        "item or its length is outside [1, FIA_SLATE_MAX_ITEMS]");
+      if (flags[2])
+        return fail(c, FIA_ERR_STATE, "a query's user or one of its slate items has no Hessian cache: it was not "
+                                      "among the queries of the last fia_prepare_for");
+    }
+    return FIA_OK;
+  })
+}
+
+int fia_slate_batch(fia_ctx* c, int64_t Q, const int32_t* qu, const int64_t* slate_offsets, int64_t total_items,
+                    const int32_t* slate_item, const double* slate_weight, const int64_t* offsets, int64_t total_rel,
+                    int32_t* rel_idx, double* influence, double* x_out, double* value, int K, int64_t* topk_pos,
+                    int64_t* topk_idx, double* topk_val, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    // the batch bounds come first: nothing of an oversized batch is looked at
+    if (Q < 0 || Q > FIA_SLATE_MAX_TOTAL_ITEMS)
+      return fail(c, FIA_ERR_INVALID, "num_queries out of range [0, 2^30]: split the batch");
+    // a half record per (query, item), indexed in 32 bits
+    if (total_items < 0 || total_items > FIA_SLATE_MAX_TOTAL_ITEMS)
+      return fail(c, FIA_ERR_INVALID, "total_items out of range [0, 2^30]: split the batch");
+    // a rating's position inside its query's related list is kept in 32 bits by the top-K selection
+    if (total_rel < 0 || total_rel > FIA_SLATE_MAX_TOTAL_REL)
+      return fail(c, FIA_ERR_INVALID, "total_rel out of range [0, 2^31 - 1]: split the batch");
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
+    if (K < 0 || K > FIA_MAX_TOPK) return fail(c, FIA_ERR_INVALID, "K must be in [0, FIA_MAX_TOPK]");
+    if (K > 0 && (!topk_pos || !topk_idx || !topk_val)) return fail(c, FIA_ERR_INVALID, "null top-K output");
+    if (!rel_idx && !influence && !x_out && !value && K == 0)
+      return fail(c, FIA_ERR_INVALID, "no output requested (rel_idx, influence, x_out, value, top-K)");
+    if (Q == 0) return FIA_OK;
+    if (!qu || !slate_offsets || !offsets || (total_items > 0 && (!slate_item || !slate_weight)))
+      return fail(c, FIA_ERR_INVALID, "null query, slate or offset array");
+    if (!fia::slate_supported(c->p.model, c->p.k))
+      return fail(c, FIA_ERR_UNSUPPORTED,
+                  "fia_slate_batch is built for MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32}; the large-k models "
+                  "are not supported yet");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_slate_batch"); rc != FIA_OK) return rc;
+    // the Gram caches of a pending small-k pass are read: join it, as fia_pair_batch does
+    if (hipError_t es = fia::join_prepare(c, s); es != hipSuccess) return hip_fail(c, es, "fia_slate_batch");
+    hipError_t e = fia::slate_batch(c, Q, qu, slate_offsets, total_items, slate_item, slate_weight, offsets,
+                                    total_rel, rel_idx, influence, x_out, value, K, topk_pos, topk_idx, topk_val, s);
+    if (e != hipSuccess) return hip_fail(c, e, "fia_slate_batch");
+    return FIA_OK;
+  })
+}
+
 int fia_set_profiling(fia_ctx* c, int phase_mask) {
   if (!c) return FIA_ERR_INVALID;
   c->profiling = (unsigned)phase_mask & ((1u << FIA_NUM_PHASES) - 1u);

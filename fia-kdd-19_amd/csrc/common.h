@@ -593,6 +593,22 @@ hipError_t pair_batch(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
                       const int64_t* offsets, int64_t total_rel, int32_t* rel_idx, double* influence, double* x_out,
                       double* diff, int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val, hipStream_t s);
 
+// fia_count_related_slate / fia_slate_batch (slate.hip): the system of f = sum_l w_l r-hat(u, i_l)
+// over theta_t = (theta_u, theta_i1 .. theta_im) and the list R_u ++ C_i1 ++ .. ++ C_im, an arrowhead
+// solved block by block (two Ds triangles in LDS whatever m); every small-k size (slate_supported);
+// `cover`: the count also flags entities outside a fia_prepare_for cover.  Scratch: c->qscan and
+// c->flag (the count), c->rec (a half record per (query, item)), c->coff (the tiles' first queries),
+// c->nch (the queries' list starts), c->tkeys (their sorted items and which are scored),
+// c->cand_pos, c->cand_val
+bool slate_supported(int model, int k);
+hipError_t count_related_slate(fia_ctx* c, int64_t Q, const int32_t* qu, const int64_t* slate_offsets,
+                               int64_t total_items, const int32_t* slate_item, int64_t* offsets, bool cover,
+                               hipStream_t s);
+hipError_t slate_batch(fia_ctx* c, int64_t Q, const int32_t* qu, const int64_t* slate_offsets, int64_t total_items,
+                       const int32_t* slate_item, const double* slate_weight, const int64_t* offsets,
+                       int64_t total_rel, int32_t* rel_idx, double* influence, double* x_out, double* value, int K,
+                       int64_t* topk_pos, int64_t* topk_idx, double* topk_val, hipStream_t s);
+
 // phase event helpers (no-ops unless profiling)
 void phase_begin(fia_ctx* c, int phase, hipStream_t s);
 void phase_end(fia_ctx* c, int phase, hipStream_t s);

@@ -16,6 +16,7 @@ FIA_OK = 0
 FIA_MODEL_MF = 0
 FIA_MODEL_NCF = 1
 FIA_MAX_TOPK = 64
+FIA_SLATE_MAX_ITEMS = 64
 FIA_NUM_PHASES = 5
 PHASES = ("prepare", "solve", "score", "topk", "chunks")
 
@@ -49,6 +50,9 @@ SIGNATURES = {
                                           ctypes.c_int, _P, _P, _P]),
     "fia_count_related_pair": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
     "fia_pair_batch": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
+    "fia_count_related_slate": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
+    "fia_slate_batch": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P,
+                                       _P, _P]),
     "fia_num_params": (ctypes.c_int, [_P]),
     "fia_set_profiling": (ctypes.c_int, [_P, ctypes.c_int]),
     "fia_profile_read": (ctypes.c_int, [_P, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(_I64)]),
@@ -556,6 +560,81 @@ class Context(object):
                                      _ptr(rel_idx), _ptr(influence), _ptr(x), _ptr(diff), K, _ptr(topk_pos),
                                      _ptr(topk_idx), _ptr(topk_val), _stream())
         self._check(rc, "fia_pair_batch")
+
+    def count_related_slate(self, qu, slate_offsets, slate_item, offsets=None, want_total=True):
+        """fia_count_related_slate: offsets (int64 [Q + 1]) of the slate queries' related lists
+        R_u ++ C_i1 ++ .. ++ C_im and, with want_total, their total on the host (then bad ids,
+        repeated items, bad slate lengths and entities outside a prepare_for cover raise).  Slate q
+        is slate_item[slate_offsets[q] : slate_offsets[q + 1]]."""
+        import torch
+        for t, name in ((qu, "qu"), (slate_item, "slate_item")):
+            self._need_int32(t, name)
+        Q = qu.numel()
+        if slate_offsets.dtype != torch.int64 or slate_offsets.numel() != Q + 1:
+            raise TypeError("slate_offsets must be a torch.int64 tensor of Q + 1 values")
+        if not (slate_offsets.is_cuda and slate_offsets.is_contiguous()):
+            raise TypeError("slate_offsets must be a contiguous device (cuda) tensor")
+        if offsets is None:
+            offsets = torch.empty(Q + 1, dtype=torch.int64, device=self.torch_device)
+        total = ctypes.c_int64(0)
+        rc = self.lib.fia_count_related_slate(self.h, Q, _ptr(qu), _ptr(slate_offsets), slate_item.numel(),
+                                              _ptr(slate_item), _ptr(offsets),
+                                              ctypes.byref(total) if want_total else None, _stream())
+        self._check(rc, "fia_count_related_slate")
+        return offsets, (total.value if want_total else None)
+
+    def slate_batch(self, qu, slate_offsets, slate_item, slate_weight, offsets, total, rel_idx=None, influence=None,
+                    x=None, value=None, K=0, topk_pos=None, topk_idx=None, topk_val=None):
+        """fia_slate_batch: for every slate query (qu; its items; its weights) the influence of every
+        rating of R_u ++ C_i1 ++ .. ++ C_im on f = sum_l w_l r-hat(u, i_l) -- one system over
+        (theta_u, theta_i1 .. theta_im), solved once -- into influence (float64 [total]), the train
+        rows into rel_idx (int32 [total]), x = H^-1 v into x (float64 [Ds * (total_items + Q)], query
+        q's at Ds * (slate_offsets[q] + q), the extended reference theta order), f into value
+        (float64 [Q]) and, with K, the K ratings of largest |influence| per query (topk_pos /
+        topk_idx int64 [Q * K], topk_val float64 [Q * K]).  offsets / total as count_related_slate
+        returns them."""
+        import torch
+        for t, name in ((qu, "qu"), (slate_item, "slate_item"), (rel_idx, "rel_idx")):
+            self._need_int32(t, name)
+        Q = qu.numel()
+        TI = slate_item.numel()
+        if slate_weight.numel() != TI:
+            raise ValueError("slate_item and slate_weight must have the same length")
+        for t, name in ((slate_offsets, "slate_offsets"), (offsets, "offsets")):
+            if t.dtype != torch.int64 or t.numel() != Q + 1:
+                raise TypeError("%s must be a torch.int64 tensor of Q + 1 values" % name)
+        for t, name in ((slate_weight, "slate_weight"), (influence, "influence"), (x, "x"), (value, "value"),
+                        (topk_val, "topk_val")):
+            if t is not None and t.dtype != torch.float64:
+                raise TypeError("%s must be a torch.float64 tensor" % name)
+        for t, name in ((topk_pos, "topk_pos"), (topk_idx, "topk_idx")):
+            if t is not None and t.dtype != torch.int64:
+                raise TypeError("%s must be a torch.int64 tensor" % name)
+        for t, name in ((qu, "qu"), (slate_offsets, "slate_offsets"), (slate_item, "slate_item"),
+                        (slate_weight, "slate_weight"), (offsets, "offsets"), (rel_idx, "rel_idx"),
+                        (influence, "influence"), (x, "x"), (value, "value"), (topk_pos, "topk_pos"),
+                        (topk_idx, "topk_idx"), (topk_val, "topk_val")):
+            if t is not None and not (t.is_cuda and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous device (cuda) tensor" % name)
+        # (an oversized total is the library's to refuse, before it looks at any array)
+        if 0 <= total < 2 ** 31:
+            for t, name in ((rel_idx, "rel_idx"), (influence, "influence")):
+                if t is not None and t.numel() < total:
+                    raise ValueError("%s holds %d values, the batch has %d related ratings" % (name, t.numel(), total))
+        Ds = self.num_params() // 2
+        if x is not None and x.numel() < Ds * (TI + Q):
+            raise ValueError("x holds %d values, %d queries with %d items need %d" % (x.numel(), Q, TI, Ds * (TI + Q)))
+        if value is not None and value.numel() < Q:
+            raise ValueError("value holds %d values, the batch has %d queries" % (value.numel(), Q))
+        K = int(K)
+        if K > 0 and (topk_pos is None or topk_idx is None or topk_val is None
+                      or min(topk_pos.numel(), topk_idx.numel(), topk_val.numel()) < Q * K):
+            raise ValueError("top-K outputs must hold Q * K values")
+        rc = self.lib.fia_slate_batch(self.h, Q, _ptr(qu), _ptr(slate_offsets), TI, _ptr(slate_item),
+                                      _ptr(slate_weight), _ptr(offsets), int(total), _ptr(rel_idx), _ptr(influence),
+                                      _ptr(x), _ptr(value), K, _ptr(topk_pos), _ptr(topk_idx), _ptr(topk_val),
+                                      _stream())
+        self._check(rc, "fia_slate_batch")
 
     # ---- profiling ----
     def set_profiling(self, on, phases=None):

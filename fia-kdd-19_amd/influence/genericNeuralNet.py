@@ -934,6 +934,100 @@ class GenericNeuralNet(object):
             out["topk_val"] = tv[:Q * K].cpu().numpy().reshape(Q, K)
         return out
 
+    def _checked_slates(self, users, slates, weights):
+        """The host-side checks of get_slate_influence_batch (ValueError): returns (users int32 [Q],
+        slate_offsets int64 [Q + 1], items int32 [total], weights float64 [total])."""
+        def ints(a, what):
+            a = np.asarray(a)
+            if a.ndim != 1 or (a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer))):
+                raise ValueError("%s must be a 1-d sequence of integers (got dtype %s, shape %s)" % (what, a.dtype,
+                                                                                                    a.shape))
+            return a.astype(np.int64)
+        u = ints(users, "users")
+        if u.size and (u.min() < 0 or u.max() >= self.num_users):
+            raise ValueError("users must lie in [0, %d)" % self.num_users)
+        if len(slates) != u.size:
+            raise ValueError("%d users but %d slates" % (u.size, len(slates)))
+        if weights is not None and len(weights) != u.size:
+            raise ValueError("%d users but %d weight lists" % (u.size, len(weights)))
+        items, wts, off = [], [], [0]
+        for q in range(u.size):
+            it = ints(slates[q], "slates[%d]" % q)
+            if not 1 <= it.size <= _lib.FIA_SLATE_MAX_ITEMS:
+                raise ValueError("slates[%d] holds %d items, not in [1, %d]" % (q, it.size, _lib.FIA_SLATE_MAX_ITEMS))
+            if it.min() < 0 or it.max() >= self.num_items:
+                raise ValueError("slates[%d] must lie in [0, %d)" % (q, self.num_items))
+            if np.unique(it).size != it.size:
+                raise ValueError("slates[%d] repeats an item" % q)
+            if weights is None:
+                w = 1.0 / np.log2(np.arange(it.size) + 2.0)        # DCG's discount, rank from 0
+            else:
+                try:
+                    w = np.asarray(weights[q], np.float64)
+                except (TypeError, ValueError):
+                    raise ValueError("weights[%d] must be numbers" % q)
+                if w.shape != it.shape:
+                    raise ValueError("weights[%d] holds %s values for %d items" % (q, w.shape, it.size))
+                if not np.isfinite(w).all():
+                    raise ValueError("weights[%d] must be finite" % q)
+            items.append(it)
+            wts.append(w)
+            off.append(off[-1] + it.size)
+        cat = lambda parts, dt: np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(0), dt)
+        return np.ascontiguousarray(u, np.int32), np.asarray(off, np.int64), cat(items, np.int32), cat(wts, np.float64)
+
+    def get_slate_influence_batch(self, users, slates, weights=None, K=1, full=True, return_x=True):
+        """Which ratings shape a user's ranked list (one fia_slate_batch call): query t is user
+        users[t] (a user id, not a test index) with the ranked items slates[t] (1 to
+        FIA_SLATE_MAX_ITEMS distinct item ids) and the explained number is the weighted sum
+        f = sum_l weights[t][l] * r-hat(u, i_l); the default weights are DCG's discount
+        1 / log2(rank + 2), rank from 0.  Its system is its own -- theta_t = (theta_u, theta_i1 ..
+        theta_im), the related list R_u ++ C_i1 ++ .. ++ C_im, one Hessian, one solve
+        (include/fia.h) -- not the weighted sum of get_influence_batch results.
+        influence[offsets[t] + p] is the predicted change of f when the p-th rating of that list is
+        removed.  Equal lengths, integer in-range ids, the slate lengths, distinct items per slate,
+        finite weights and K (an integer in [0, FIA_MAX_TOPK]) are checked on the host (ValueError)
+        before any GPU call.  Returns dict(offsets int64 [Q + 1], value float64 [Q]; with full
+        rel_idx int64 and influence float64 [total]; with return_x x, a list of Q float64 vectors
+        [(m_t + 1) Ds] in the extended reference theta order (MF [p_u, q_1 .. q_m, b_u, b_1 .. b_m],
+        NCF [Pm_u, Qm_1 .., Pg_u, Qg_1 ..]); with K topk_pos, topk_idx int64 [Q, K] and topk_val
+        float64 [Q, K] by |influence|, ties to the lower position, -1 / -1 / NaN in unused slots) as
+        numpy arrays.  Every small-k size is served; the large-k models raise FIAError
+        (unsupported)."""
+        if isinstance(K, bool) or int(K) != K or not 0 <= int(K) <= _lib.FIA_MAX_TOPK:
+            raise ValueError("K must be in [0, %d]" % _lib.FIA_MAX_TOPK)
+        K = int(K)
+        u, soff, items, wts = self._checked_slates(users, slates, weights)
+        import torch
+        Q, TI = u.size, items.size
+        dev = self.ctx.torch_device
+        up = lambda a: torch.from_numpy(a).to(dev) if a.size else torch.empty(1, dtype=torch.from_numpy(a).dtype,
+                                                                              device=dev)[:0]
+        qu, so, it, wt = up(u), torch.from_numpy(soff).to(dev), up(items), up(wts)
+        # (the count rejects entities outside a prepare_for cover)
+        offsets, total = self.ctx.count_related_slate(qu, so, it)
+        Ds = self._host_num_params() // 2
+        f64 = lambda m: torch.empty(max(m, 1), dtype=torch.float64, device=dev)
+        i64 = lambda m: torch.empty(max(m, 1), dtype=torch.int64, device=dev)
+        rel = torch.empty(max(total, 1), dtype=torch.int32, device=dev) if full else None
+        infl = f64(total) if full else None
+        x = f64(Ds * (TI + Q)) if return_x else None
+        value = f64(Q)
+        tp, ti, tv = (i64(Q * K), i64(Q * K), f64(Q * K)) if K else (None, None, None)
+        self.ctx.slate_batch(qu, so, it, wt, offsets, total, rel, infl, x, value, K, tp, ti, tv)
+        out = dict(offsets=offsets.cpu().numpy(), value=value[:Q].cpu().numpy())
+        if full:
+            out["rel_idx"] = rel[:total].cpu().numpy().astype(np.int64)
+            out["influence"] = infl[:total].cpu().numpy()
+        if return_x:
+            xs = x[:Ds * (TI + Q)].cpu().numpy()
+            out["x"] = [xs[Ds * (soff[q] + q):Ds * (soff[q + 1] + q + 1)].copy() for q in range(Q)]
+        if K:
+            out["topk_pos"] = tp[:Q * K].cpu().numpy().reshape(Q, K)
+            out["topk_idx"] = ti[:Q * K].cpu().numpy().reshape(Q, K)
+            out["topk_val"] = tv[:Q * K].cpu().numpy().reshape(Q, K)
+        return out
+
     def _predict_device(self, qu, qi):
         """r-hat(u, i) in fp64 on the device from the uploaded (float32) parameter tables."""
         import torch

@@ -34,6 +34,9 @@
  *   (none: one test point per call, mf:179 -- which     fia_count_related_pair + fia_pair_batch
  *     ratings put item i above item j for a user, the
  *     influence on r-hat(u, i) - r-hat(u, j))
+ *   (none: one test point per call, mf:179 -- which     fia_count_related_slate + fia_slate_batch
+ *     ratings shape a user's ranked list, the influence
+ *     on sum_l w_l r-hat(u, i_l))
  *
  * Conventions
  *   - All array arguments are DEVICE pointers owned by the caller (PyTorch).
@@ -662,6 +665,92 @@ int fia_pair_batch(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, con
                    double* diff,                   /* device [Q], nullable                       */
                    int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val,   /* device [Q*K] */
                    void* stream);
+
+/* Slates: which ratings shape a user's top-N list.  The explained number is a weighted sum over a
+ * ranked list, f = sum_l w_l * r-hat(u, i_l) -- the caller picks the weights: 1 / log2(rank + 1) for a
+ * DCG-like score, (1, -1) for fia_pair_batch's gap.  As with the pair call, the weighted sum of m
+ * fia_query_batch results is not FIA's answer for f: the single queries restrict to different parameter
+ * sets, normalise by different n, and each re-solves the shared user block against one item alone.
+ * Slate query q = (u; i_1 .. i_m; w_1 .. w_m) = (q_user[q]; slate_item[slate_offsets[q] ..
+ * slate_offsets[q + 1]); slate_weight[likewise]), the items distinct, 1 <= m <= FIA_SLATE_MAX_ITEMS.
+ * Side block size Ds = k + 1 (MF) or 2k (NCF), D_q = (m + 1) * Ds.
+ *   theta_t = (theta_u, theta_i1, .., theta_im)
+ *   rel     = where(user == u) ++ where(item == i_1) ++ .. ++ where(item == i_m), each in ascending
+ *             train-row order; n = |rel|.  A train row (u, i_l) sits in rel twice; no row three times.
+ *   For position p with train row (a, b, y): e_p = r-hat(a, b) - y and g_p = d r-hat(a, b) / d theta_t,
+ *             whose user block is zero unless a == u and whose block l unless b == i_l -- whichever list
+ *             the position is in.
+ *   H       = (2/n) sum_p (g_p g_p^T + e_p d2 r-hat_p) + wd * diag(M) + damping * I.  From the caches, with
+ *             v^l = d r-hat(u, i_l) / d (theta_u, theta_il), A_u / B_i the entity Grams, (cd_l, es_l) = (rows
+ *             of (u, i_l) in train, the sum of their residuals) and E the diagonal of the own pair's
+ *             d2 r-hat / d theta_i d theta_u (MF: 1 on the k embedding coordinates, 0 on the bias; NCF: W3g
+ *             on the GMF coordinates, 0 on the MLP coordinates):
+ *               H_uu = (2/n) (A_u + sum_l cd_l v^l_u v^l_u^T)       H_ll = (2/n) (B_il + cd_l v^l_l v^l_l^T)
+ *               H_lu = (2/n) 2 (cd_l v^l_l v^l_u^T + es_l diag(E))  H_lm = 0 for l != m
+ *             plus the diagonal terms: an arrowhead, block diagonal when the user has rated no slate item.
+ *   v       = d f / d theta_t = (sum_l w_l v^l_u, w_1 v^1_1, .., w_m v^m_m)
+ *   x       = H^-1 v: exact fp64, block by block -- each item block's LDL^T, the Schur complement of the
+ *             rated items taken out of the user block, the user block's LDL^T, then the rated items'
+ *             back-substitution; nothing assumed about a pivot's sign
+ *   influence[offsets[q] + p] = x . (2 e_p g_p + wd * M * theta_t) / n     fia_query_batch's expression
+ *   value[q] = f                                                           current parameters, fp64
+ *   x_out   : query q's x starts at Ds * (slate_offsets[q] + q), D_q doubles in the reference theta order,
+ *             extended: MF [p_u, q_1 .. q_m, b_u, b_1 .. b_m], NCF [Pm_u, Qm_1 .. Qm_m, Pg_u, Qg_1 .. Qg_m]
+ * With m = 2 and w = (1, -1) this is fia_pair_batch's system, with m = 1 and w = (1) fia_query_batch's
+ * (equal values; the elimination order differs, so not equal bits).  A zero weight is an ordinary
+ * weight: the item stays in theta_t and in rel.
+ * topk (K in [0, FIA_MAX_TOPK]; 0 = off): per query, as fia_pair_batch -- position in the slate's own
+ * related list (topk_pos), train row (topk_idx), signed value (topk_val), device arrays [Q*K]; unused
+ * slots hold -1 / -1 / NaN.
+ *   - An id outside [0, num_users) x [0, num_items) is never used as an index and counts as n = 0; the
+ *     query's value and x are NaN.  A repeated item, m = 0 and m > FIA_SLATE_MAX_ITEMS are treated alike.
+ *   - n = 0 with good ids (an empty user and empty items) writes no ratings, a NaN x and the finite f.
+ *   - No floating-point atomics and every sum in slate order: a query's bits depend on (u, the items in
+ *     their order, the weights) alone, not on where it sits in the batch or on what else is in it.
+ * fia_count_related_slate: fia_count_related_pair's contract for the slate list (offsets device int64
+ * [Q+1]; with total_out the total is copied to the host, the stream synchronised, bad ids, repeated
+ * items and bad slate lengths reported as FIA_ERR_INVALID, and a query whose u or one of whose items is
+ * outside a fia_prepare_for cover as FIA_ERR_STATE).  Without total_out such queries count zero.  Needs
+ * the index only.
+ * fia_slate_batch: rel_idx (int32 train rows), influence, x_out and value are each nullable; all four
+ * NULL with K == 0 is FIA_ERR_INVALID.  total_rel must equal offsets[Q], total_items slate_offsets[Q].
+ * With influence NULL and K > 0 nothing of length total_rel is written.  num_queries == 0 returns FIA_OK
+ * and launches nothing.  Batch limits: total_items and num_queries <= FIA_SLATE_MAX_TOTAL_ITEMS (2^30: a
+ * half record per (query, item), indexed in 32 bits), total_rel <= FIA_SLATE_MAX_TOTAL_REL (2^31 - 1: the
+ * top-K keeps a 32-bit position); a larger batch is refused with FIA_ERR_INVALID before anything is
+ * reserved or launched -- split it.  Checks run in fia_pair_batch's order: bounds, state, outputs, the
+ * empty batch, nulls, support.  Needs params, index and a prepare (else FIA_ERR_STATE).  After
+ * fia_prepare_for the cover must hold u and every slate item (fia_prepare_for with the pairs (u, i_l));
+ * the results are then bitwise those after fia_prepare.  Ordered on `stream`, no host synchronisation; it
+ * reads the entity Gram caches, so it joins a pending small-k Gram pass as fia_pair_batch does.  Stores
+ * are per element: the outputs need only their types' natural alignment.
+ * Sizes: MF k in {8, 16, 32, 64} and NCF k in {8, 16, 32} -- every small-k size, the two that
+ * fia_pair_batch refuses included: a workgroup holds two packed Ds triangles whatever m (MF k=64: 2 x
+ * 2,145 doubles).  The large-k models are FIA_ERR_UNSUPPORTED.
+ * Phases (fia_set_profiling): 4 the count and scan (fia_count_related_slate) and the related rows,
+ * 1 the solves, 2 the scoring, 3 the top-K.  fia_version stays 100: no existing signature, struct or
+ * constant changed. */
+#define FIA_SLATE_MAX_ITEMS 64
+#define FIA_SLATE_MAX_TOTAL_ITEMS (1LL << 30)
+#define FIA_SLATE_MAX_TOTAL_REL ((1LL << 31) - 1)
+int fia_count_related_slate(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user,
+                            const int64_t* slate_offsets,   /* device [Q+1]                              */
+                            int64_t total_items,            /* == slate_offsets[Q]                       */
+                            const int32_t* slate_item,      /* device [total_items]                      */
+                            int64_t* offsets,               /* device [Q+1], written                     */
+                            int64_t* total_out,             /* host, nullable                            */
+                            void* stream);
+int fia_slate_batch(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int64_t* slate_offsets,
+                    int64_t total_items, const int32_t* slate_item,
+                    const double* slate_weight,     /* device [total_items]                        */
+                    const int64_t* offsets,         /* device [Q+1], from fia_count_related_slate */
+                    int64_t total_rel,              /* == offsets[Q]                               */
+                    int32_t* rel_idx,               /* device [total_rel], nullable                */
+                    double* influence,              /* device [total_rel], nullable                */
+                    double* x_out,                  /* device [Ds * (total_items + Q)], nullable   */
+                    double* value,                  /* device [Q], nullable                        */
+                    int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val,   /* device [Q*K] */
+                    void* stream);
 
 /* Number of restricted parameters D of the registered model (0 if none). */
 int fia_num_params(const fia_ctx* ctx);
