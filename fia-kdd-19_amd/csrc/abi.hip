@@ -831,6 +831,38 @@ int fia_pair_batch(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, 
   })
 }
 
+int fia_pair_flip(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int32_t* qj, const double* margin,
+                  int max_set, int32_t* set_size, int32_t* set_row, double* set_val, double* first_order,
+                  double* newton, double* dtheta, double* diff, void* stream) {
+  if (!c) return FIA_ERR_INVALID;
+  FIA_GUARDED(c, {
+    // the batch bounds come first: nothing of an oversized batch is looked at
+    if (Q < 0 || Q > FIA_PAIR_MAX_QUERIES)
+      return fail(c, FIA_ERR_INVALID, "num_queries out of range [0, 2^30]: split the batch");
+    if (max_set < 1 || max_set > FIA_FLIP_MAX_SET)
+      return fail(c, FIA_ERR_INVALID, "max_set must be in [1, FIA_FLIP_MAX_SET]");
+    if (int rc = check_prepared(c); rc != FIA_OK) return rc;
+    if (!set_size && !set_row && !set_val && !first_order && !newton && !dtheta && !diff)
+      return fail(c, FIA_ERR_INVALID,
+                  "no output requested (set_size, set_row, set_val, first_order, newton, dtheta, diff)");
+    if (Q == 0) return FIA_OK;
+    if (!qu || !qi || !qj) return fail(c, FIA_ERR_INVALID, "null query array");
+    if (!fia::pair_supported(c->p.model, c->p.k))
+      return fail(c, FIA_ERR_UNSUPPORTED,
+                  "fia_pair_flip is built for MF k in {8, 16, 32} and NCF k in {8, 16} (the three-block system in "
+                  "one workgroup's LDS); MF k = 64, NCF k = 32 and the large-k models are not supported yet");
+    DeviceGuard g(c->device);
+    hipStream_t s = as_stream(stream);
+    if (int rc = enter_stream(c, s, "fia_pair_flip"); rc != FIA_OK) return rc;
+    // the Gram caches of a pending small-k pass are read: join it, as fia_pair_batch does
+    if (hipError_t es = fia::join_prepare(c, s); es != hipSuccess) return hip_fail(c, es, "fia_pair_flip");
+    hipError_t e = fia::pair_flip(c, Q, qu, qi, qj, margin, max_set, set_size, set_row, set_val, first_order, newton,
+                                  dtheta, diff, s);
+    if (e != hipSuccess) return hip_fail(c, e, "fia_pair_flip");
+    return FIA_OK;
+  })
+}
+
 int fia_count_related_slate(fia_ctx* c, int64_t Q, const int32_t* qu, const int64_t* slate_offsets,
                             int64_t total_items, const int32_t* slate_item, int64_t* offsets, int64_t* total_out,
                             void* stream) {

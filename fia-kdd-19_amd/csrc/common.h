@@ -593,6 +593,15 @@ hipError_t pair_batch(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* q
                       const int64_t* offsets, int64_t total_rel, int32_t* rel_idx, double* influence, double* x_out,
                       double* diff, int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val, hipStream_t s);
 
+// fia_pair_flip (flip.hip): per pair query the greedy first-order set of the user's own ratings that
+// closes the gap (the max_set smallest negative values of R_u, a sequential stop rule) and the
+// re-solved three-block system with that set removed; the sizes of pair_supported; scratch: c->rec
+// (pair_batch's half records), c->gxq (the gap and the sizes when the caller takes neither, the
+// members' list entries)
+hipError_t pair_flip(fia_ctx* c, int64_t Q, const int32_t* qu, const int32_t* qi, const int32_t* qj,
+                     const double* margin, int max_set, int32_t* set_size, int32_t* set_row, double* set_val,
+                     double* first_order, double* newton, double* dtheta, double* diff, hipStream_t s);
+
 // fia_count_related_slate / fia_slate_batch (slate.hip): the system of f = sum_l w_l r-hat(u, i_l)
 // over theta_t = (theta_u, theta_i1 .. theta_im) and the list R_u ++ C_i1 ++ .. ++ C_im, an arrowhead
 // solved block by block (two Ds triangles in LDS whatever m); every small-k size (slate_supported);

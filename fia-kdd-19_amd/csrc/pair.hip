@@ -28,37 +28,13 @@
 //                  every (tile, query) segment selects into slot tile + q
 //   k_cand_merge (score_cand.hip), k_pair_topk_idx   the per-query merge, then topk_idx from the position
 // No floating-point atomics; a query's values depend on (u, i, j) alone.
-#include "cand.h"
+#include "pair.h"
 #include "scan.h"
-#include "solve.h"
 
 namespace fia {
 namespace {
 
 constexpr int kPairRecGrid = 1 << 20;   // most workgroups of the per-query kernels (grid-stride)
-
-// The sizes whose packed D3 triangle, vectors and (NCF) staged W1 fit one workgroup's LDS
-template <class M>
-constexpr bool pair_built() {
-  return M::ncf ? M::K <= 16 : M::K <= 32;
-}
-
-// The scoring record k_pair_solve writes and k_pair_score reads: two HALVES per query, 2 q for
-// (user, item i) and 2 q + 1 for item j, so that coop_dots (cand.h) picks the item block of a
-// position by the half's index.  MF: the layout below; NCF: CandRecNCF of cand.h.  The head
-// (1 / n, c_q) and the user entries are those of half 0.  Offsets in doubles.
-template <int K>
-struct PairRecMF : CandHead {
-  static constexpr int x_user = head;               // [K] x at p_u
-  static constexpr int x_item = head + K;           // [K] x at q_i (half 0) / q_j (half 1)
-  static constexpr int x_bias_user = head + 2 * K;
-  static constexpr int x_bias_item = head + 2 * K + 1;
-  static constexpr int size = head + 2 * K + 2;
-};
-template <class M>
-constexpr int pair_half() {
-  return M::ncf ? CandRecNCF<M::K>::size : PairRecMF<M::K>::size;
-}
 
 struct PairArgs : ModelArgs {
   int64_t Q, total;
@@ -73,10 +49,6 @@ struct PairArgs : ModelArgs {
   int32_t* tile_q;          // [tiles]: the query of each tile's first position (k_pair_solve)
   double* rec;              // [Q * 2 * pair_half]
 };
-
-__device__ __forceinline__ bool pair_ids_ok(int32_t u, int32_t i, int32_t j, int64_t U, int64_t I) {
-  return u >= 0 && u < U && i >= 0 && i < I && j >= 0 && j < I;
-}
 
 // Position `pos` of the related list of (u, i, j) (ids in range, i != j): its list (0 user, 1 item
 // i, 2 item j; -1 past the list's end) and its index into that side's list arrays
@@ -171,22 +143,6 @@ __global__ void k_pair_rel(PairArgs A, int32_t* __restrict__ rel) {
     for (int64_t p = threadIdx.x; p < ln[l] && base + p < end; p += blockDim.x) rel[base + p] = src[p];
     base += ln[l];
   }
-}
-
-// coordinate a of the 3-block order -> the reference theta order, extended:
-// MF [p_u, q_i, q_j, b_u, b_i, b_j], NCF [Pm_u, Qm_i, Qm_j, Pg_u, Qg_i, Qg_j]
-template <class M>
-__device__ __forceinline__ int pair_ref_index(int a) {
-  constexpr int K = M::K, Ds = M::Ds;
-  const int b = a / Ds, c = a - b * Ds;
-  if constexpr (!M::ncf) return c < K ? b * K + c : 3 * K + b;
-  else return c < K ? b * K + c : 3 * K + b * K + (c - K);
-}
-
-template <class M>
-constexpr int64_t pair_lds_bytes() {
-  constexpr int64_t K = M::K, D = M::D, D3 = 3 * M::Ds;
-  return 8 * (D3 * (D3 + 1) / 2 + 4 * D + 3 * D3 + 4 * K + 8 + (M::ncf ? 2 * K * K + K + K * (K / 2) + 2 * K : 8));
 }
 
 template <class M>

@@ -18,6 +18,7 @@ FIA_MODEL_NCF = 1
 FIA_MAX_TOPK = 64
 FIA_SLATE_MAX_ITEMS = 64
 FIA_NUM_PHASES = 5
+FIA_FLIP_MAX_SET = 64
 PHASES = ("prepare", "solve", "score", "topk", "chunks")
 
 _ERR = {1: "invalid argument", 2: "HIP error", 3: "bad call order", 4: "unsupported", 5: "out of memory"}
@@ -50,6 +51,7 @@ SIGNATURES = {
                                           ctypes.c_int, _P, _P, _P]),
     "fia_count_related_pair": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, ctypes.POINTER(_I64), _P]),
     "fia_pair_batch": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P]),
+    "fia_pair_flip": (ctypes.c_int, [_P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "fia_count_related_slate": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
     "fia_slate_batch": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, ctypes.c_int, _P, _P,
                                        _P, _P]),
@@ -560,6 +562,47 @@ class Context(object):
                                      _ptr(rel_idx), _ptr(influence), _ptr(x), _ptr(diff), K, _ptr(topk_pos),
                                      _ptr(topk_idx), _ptr(topk_val), _stream())
         self._check(rc, "fia_pair_batch")
+
+    def pair_flip(self, qu, qi, qj, max_set, margin=None, set_size=None, set_row=None, set_val=None,
+                  first_order=None, newton=None, dtheta=None, diff=None):
+        """fia_pair_flip: for every pair query (qu, qi, qj) the greedy first-order set of the user's
+        own ratings that puts j above i -- the most negative values of R_u, taken while
+        diff + margin + their running sum >= 0 and fewer than max_set are taken -- into set_size
+        (int32 [Q]), set_row (int32 [Q * max_set] train rows, -1 unused), set_val (float64
+        [Q * max_set], NaN unused) and first_order (float64 [Q]); the re-solved system's answer for
+        that set into newton (float64 [Q]) and dtheta (float64 [Q * 3 * D / 2], the extended
+        reference theta order); the gap into diff (float64 [Q]).  margin: float64 [Q] >= 0 or None
+        (0).  Every output may be None, not all."""
+        import torch
+        for t, name in ((qu, "qu"), (qi, "qi"), (qj, "qj"), (set_size, "set_size"), (set_row, "set_row")):
+            self._need_int32(t, name)
+        Q = qu.numel()
+        if qi.numel() != Q or qj.numel() != Q:
+            raise ValueError("qu, qi and qj must have the same length")
+        if isinstance(max_set, bool) or int(max_set) != max_set:
+            raise ValueError("max_set must be an integer")
+        max_set = int(max_set)
+        for t, name in ((margin, "margin"), (set_val, "set_val"), (first_order, "first_order"), (newton, "newton"),
+                        (dtheta, "dtheta"), (diff, "diff")):
+            if t is not None and t.dtype != torch.float64:
+                raise TypeError("%s must be a torch.float64 tensor" % name)
+        for t, name in ((qu, "qu"), (qi, "qi"), (qj, "qj"), (margin, "margin"), (set_size, "set_size"),
+                        (set_row, "set_row"), (set_val, "set_val"), (first_order, "first_order"),
+                        (newton, "newton"), (dtheta, "dtheta"), (diff, "diff")):
+            if t is not None and not (t.is_cuda and t.is_contiguous()):
+                raise TypeError("%s must be a contiguous device (cuda) tensor" % name)
+        # (a max_set out of range is the library's to refuse, before it looks at any array)
+        slots = Q * max_set if 1 <= max_set <= FIA_FLIP_MAX_SET else 0
+        for t, name, need in ((margin, "margin", Q), (set_size, "set_size", Q), (set_row, "set_row", slots),
+                              (set_val, "set_val", slots), (first_order, "first_order", Q), (newton, "newton", Q),
+                              (dtheta, "dtheta", Q * (3 * self.num_params() // 2) if dtheta is not None else 0),
+                              (diff, "diff", Q)):
+            if t is not None and t.numel() < need:
+                raise ValueError("%s holds %d values, the batch needs %d" % (name, t.numel(), need))
+        rc = self.lib.fia_pair_flip(self.h, Q, _ptr(qu), _ptr(qi), _ptr(qj), _ptr(margin), max_set, _ptr(set_size),
+                                    _ptr(set_row), _ptr(set_val), _ptr(first_order), _ptr(newton), _ptr(dtheta),
+                                    _ptr(diff), _stream())
+        self._check(rc, "fia_pair_flip")
 
     def count_related_slate(self, qu, slate_offsets, slate_item, offsets=None, want_total=True):
         """fia_count_related_slate: offsets (int64 [Q + 1]) of the slate queries' related lists

@@ -934,6 +934,90 @@ class GenericNeuralNet(object):
             out["topk_val"] = tv[:Q * K].cpu().numpy().reshape(Q, K)
         return out
 
+    def _checked_flip_args(self, n_queries, margin, max_set):
+        """Host validation of get_flip_sets' margin and max_set (no GPU call): (float64 [Q] or None,
+        int) or ValueError."""
+        if isinstance(max_set, bool) or int(max_set) != max_set or not 1 <= int(max_set) <= _lib.FIA_FLIP_MAX_SET:
+            raise ValueError("max_set must be an integer in [1, %d]" % _lib.FIA_FLIP_MAX_SET)
+        if margin is None:
+            return None, int(max_set)
+        mg = np.asarray(margin, np.float64)
+        if mg.ndim == 0:
+            mg = np.full(n_queries, float(mg))
+        if mg.ndim != 1 or mg.size != n_queries:
+            raise ValueError("margin must be a number or hold one value per test index (%d)" % n_queries)
+        if not (mg >= 0.0).all():
+            raise ValueError("margin must be >= 0 (and not NaN)")
+        return np.ascontiguousarray(mg), int(max_set)
+
+    def get_flip_sets(self, test_indices, other_items, margin=None, max_set=16, return_dtheta=False):
+        """The smallest set of a user's own ratings that puts item j above item i (one fia_pair_flip
+        call): query t is the test rating (u_t, i_t) against j = other_items[t].  The user's
+        ratings of other items with a negative fia_pair_batch value are sorted ascending (ties to
+        the lower list position) and taken while fewer than max_set are taken and diff + margin +
+        their running sum >= 0 -- ACCENT's greedy first-order set -- and the re-solved system with
+        the set removed says what it really does (include/fia.h).  margin: None (0), a number or
+        one value >= 0 per query.  The arguments are checked on the host (ValueError) and the batch
+        through the pair count (bad ids and a query outside a prepare_for cover raise as they do
+        for get_pair_influence_batch) before the call.  Returns dict(diff, margin, first_order,
+        newton float64 [Q]; set_size int64 [Q]; sets, set_vals: lists of Q arrays of their true
+        length (train rows int64, values float64); flipped_first_order = diff + first_order <
+        -margin and flipped_newton = diff + newton < -margin, bool [Q]; with return_dtheta dtheta
+        float64 [Q, 3 D / 2] in the extended reference theta order) as numpy arrays.  MF k = 64,
+        NCF k = 32 and the large-k models raise FIAError (unsupported)."""
+        oj = self._checked_other_items(test_indices, other_items, distinct=True)
+        mg, max_set = self._checked_flip_args(len(test_indices), margin, max_set)
+        import torch
+        qu, qi = self._query_tensors(test_indices)
+        Q = qu.numel()
+        dev = self.ctx.torch_device
+        qj = torch.from_numpy(oj).to(dev) if Q else torch.empty(1, dtype=torch.int32, device=dev)[:0]
+        # (the count rejects query ids out of range and entities outside a prepare_for cover)
+        self.ctx.count_related_pair(qu, qi, qj, want_total=True)
+        D3 = 3 * self._host_num_params() // 2
+        f64 = lambda m: torch.empty(max(m, 1), dtype=torch.float64, device=dev)
+        i32 = lambda m: torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+        dmg = torch.from_numpy(mg).to(dev) if (mg is not None and Q) else None
+        size, rows, vals = i32(Q), i32(Q * max_set), f64(Q * max_set)
+        first, newton, diff = f64(Q), f64(Q), f64(Q)
+        dth = f64(Q * D3) if return_dtheta else None
+        self.ctx.pair_flip(qu, qi, qj, max_set, dmg, size, rows, vals, first, newton, dth, diff)
+        size = size[:Q].cpu().numpy().astype(np.int64)
+        rows = rows[:Q * max_set].cpu().numpy().astype(np.int64).reshape(Q, max_set)
+        vals = vals[:Q * max_set].cpu().numpy().reshape(Q, max_set)
+        mgv = np.zeros(Q) if mg is None else mg
+        out = dict(diff=diff[:Q].cpu().numpy(), margin=mgv, first_order=first[:Q].cpu().numpy(),
+                   newton=newton[:Q].cpu().numpy(), set_size=size,
+                   sets=[rows[q, :max(size[q], 0)].copy() for q in range(Q)],
+                   set_vals=[vals[q, :max(size[q], 0)].copy() for q in range(Q)])
+        out["flipped_first_order"] = out["diff"] + out["first_order"] < -mgv
+        out["flipped_newton"] = out["diff"] + out["newton"] < -mgv
+        if return_dtheta:
+            out["dtheta"] = dth[:Q * D3].cpu().numpy().reshape(Q, D3)
+        return out
+
+    def get_counterfactual_explanation(self, test_idx, alternatives, margin=0.0, max_set=16, verified=True):
+        """ACCENT's outer loop for one test rating (u, i): one get_flip_sets batch over (u, i, j) for
+        j in `alternatives`, and among the alternatives whose set flips -- judged by the re-solved
+        system (flipped_newton) with `verified`, else to first order -- the one with the fewest
+        rows, ties to the earlier alternative.  Returns dict(item, rows, vals: the chosen
+        alternative, its train rows and their values, or None / None / None when no set flips;
+        index: its position in `alternatives` or -1; table: get_flip_sets' result, one entry per
+        alternative)."""
+        alts = np.asarray(alternatives)
+        if alts.ndim != 1 or alts.size == 0:
+            raise ValueError("alternatives must be a non-empty 1-d sequence of items")
+        table = self.get_flip_sets([test_idx] * alts.size, alts, margin=margin, max_set=max_set)
+        flipped = table["flipped_newton"] if verified else table["flipped_first_order"]
+        best = -1
+        for a in range(alts.size):
+            if flipped[a] and (best < 0 or table["set_size"][a] < table["set_size"][best]):
+                best = a
+        if best < 0:
+            return dict(item=None, rows=None, vals=None, index=-1, table=table)
+        return dict(item=int(alts[best]), rows=table["sets"][best], vals=table["set_vals"][best], index=best,
+                    table=table)
+
     def _checked_slates(self, users, slates, weights):
         """The host-side checks of get_slate_influence_batch (ValueError): returns (users int32 [Q],
         slate_offsets int64 [Q + 1], items int32 [total], weights float64 [total])."""

@@ -666,6 +666,63 @@ int fia_pair_batch(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, con
                    int K, int64_t* topk_pos, int64_t* topk_idx, double* topk_val,   /* device [Q*K] */
                    void* stream);
 
+/* Flip sets: the smallest set of the user's OWN ratings that puts item j above item i.  What people do
+ * with fia_pair_batch's numbers is the counterfactual explanation -- "had you not rated these three
+ * films, we would have shown you j instead of i" (ACCENT, Tran, Ghazimatin and Saha Roy, SIGIR 2021):
+ * sort the user's ratings by their influence on the gap, take the shortest prefix whose summed
+ * influence closes it.  That sum is first order, and first order is a poor guide for sets, so the call
+ * also returns what the re-solved system says the set does.
+ * Pair query q = (u, i, j); n, theta_t, M, H, v, x = H^-1 v, e_p, g_p and diff are exactly those of
+ * fia_pair_batch.  margin[q] >= 0 is a device array [Q] and may be NULL, which means 0.  max_set is in
+ * [1, FIA_FLIP_MAX_SET].
+ *   eligible  position p of the user's list R_u (ascending train row) whose item is neither i nor j
+ *             and whose val_p = x . (2 e_p g_p + wd * M * theta_t) / n -- the value fia_pair_batch
+ *             writes at that position; g_p has the user block only -- is below 0 and not NaN
+ *   order     val ascending, ties by lower list position
+ *   set       rows taken in that order while the number taken is below max_set, an eligible row is
+ *             left, and (diff + margin) + (running sum of the taken val) >= 0; the running sum is in
+ *             selection order, sequential
+ *   set_size[q]                 the number of rows taken
+ *   set_row[q * max_set + t]    the train row of the t-th, set_val[q * max_set + t] its val; unused
+ *                               slots hold -1 and NaN
+ *   first_order[q]              that running sum, +0.0 for an empty set; "flipped to first order" reads
+ *                               diff + first_order < -margin
+ *   H_S = (1/n) sum_{z in S} (2 g_z g_z^T + wd * diag(M))      b_S = (1/n) sum_{z in S} (2 e_z g_z + wd * M * theta_t)
+ *   dtheta[q * D3 ..) = (H - H_S)^-1 b_S    one exact fp64 LDL^T over the full range, nothing assumed about
+ *                               a pivot's sign, in fia_pair_batch's extended reference order
+ *   newton[q] = v . dtheta      the predicted change of the gap when S is removed; with H_S dropped it
+ *                               equals first_order.  fia_group_influence's definition with m_j = 1 on
+ *                               the three-block system.
+ *   - An empty set gives exactly +0.0 for newton and every dtheta entry, without a solve: diff + margin
+ *     < 0 already, no eligible row, or a user with no ratings but n > 0.
+ *   - An id out of range (never used as an index), i == j, or n == 0: set_size -1 and NaN in every
+ *     double output; diff is the exception and follows fia_pair_batch's rule (NaN / +0.0 / the gap).
+ *   - No floating-point atomics: a query's bits depend on (u, i, j, margin, max_set) alone; the set of a
+ *     smaller max_set is a prefix of the set of a larger one.  The result does not depend on how the
+ *     user's list is cut into tiles.
+ * Every output is nullable; all NULL is FIA_ERR_INVALID.  num_queries <= FIA_PAIR_MAX_QUERIES; checks
+ * run in fia_pair_batch's order: bounds (num_queries, max_set), state, outputs, the empty batch, nulls,
+ * support.  No count call and no offsets: nothing of length total_rel exists in this call, and the
+ * item lists C_i, C_j are never read by the selection.  Needs params, index and a prepare; after
+ * fia_prepare_for the cover must hold u, i and j, and the results are then bitwise those after
+ * fia_prepare.  Ordered on `stream`, no host synchronisation; it joins a pending small-k Gram pass.
+ * Sizes: fia_pair_batch's, MF k in {8, 16, 32} and NCF k in {8, 16}; every other size is
+ * FIA_ERR_UNSUPPORTED.  Phases: 1 the solves, 2 the selection, 3 the re-solved sets.  fia_version stays
+ * 100. */
+#define FIA_FLIP_MAX_SET 64
+int fia_pair_flip(fia_ctx* ctx, int64_t num_queries, const int32_t* q_user, const int32_t* q_item_i,
+                  const int32_t* q_item_j,
+                  const double* margin,           /* device [Q], nullable: 0                    */
+                  int max_set,
+                  int32_t* set_size,              /* device [Q], nullable                       */
+                  int32_t* set_row,               /* device [Q*max_set], nullable               */
+                  double* set_val,                /* device [Q*max_set], nullable               */
+                  double* first_order,            /* device [Q], nullable                       */
+                  double* newton,                 /* device [Q], nullable                       */
+                  double* dtheta,                 /* device [Q*D3], nullable                    */
+                  double* diff,                   /* device [Q], nullable                       */
+                  void* stream);
+
 /* Slates: which ratings shape a user's top-N list.  The explained number is a weighted sum over a
  * ranked list, f = sum_l w_l * r-hat(u, i_l) -- the caller picks the weights: 1 / log2(rank + 1) for a
  * DCG-like score, (1, -1) for fia_pair_batch's gap.  As with the pair call, the weighted sum of m
